@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X City-of-Gold engine (driver contract: one JSON line on rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--chunk C]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--chunk C] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step);
+--dump-outputs DIR also writes what the last timed step left (dump_outputs()); --full adds everything
+listed under "Also reported" below, each a run of its own after the timed steps.
 
 Headline workload (BASELINE.json metric "env-steps/sec at n_envs=65536, 4 players"; configs
 C4/C5): 65,536 environments IN TOTAL, split by index across the N ranks (8,192 per GPU at N=8:
@@ -17,7 +21,7 @@ the bytes a one-launch-per-step run leaves (tests/test_gpu_rollout.py).  No host
 (C5).  No collective on the data path; the only collectives are the timing barrier and the
 max/sum of scalars (gloo).
 
-Also reported (rank 0; the extra lines only at N=1, so a scaling run stays short):
+Also reported with --full (rank 0; the extra lines only at N=1, so a scaling run stays short):
   roofline       the dominant kernel (the trio rollout) against HBM by the bytes it moves (PMC
                  counters of the same launch shape: FETCH x 2 + WRITE, gfx950 corrections), the
                  limiter that applies (the stepping wave's instruction stream, busy fraction from
@@ -73,9 +77,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--envs-total", type=int, default=N_ENVS_TOTAL, help="envs over all ranks")
     ap.add_argument("--chunk", type=int, default=1000, help="rollout steps per kernel launch")
-    ap.add_argument("--no-extras", action="store_true", help="headline + roofline only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-asv", action="store_true", help="skip the asv time_run / time_sample grid extra")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline, the hazard census, every extra "
+                         "and the CPU baseline (off: the headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline + roofline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-asv", action="store_true",
+                    help="with --full: skip the asv time_run / time_sample grid extra")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU-baseline wall time")
     ap.add_argument("--profile-steps", type=int, default=0,
                     help="only run warmup + this many rollout steps (rocprofv3 captures); no JSON checks")
@@ -549,8 +559,49 @@ def load_stamps(name="stamps_profile.json"):
         return None
 
 
+DUMP_ENVS, DUMP_SEED = 512, 0     # record arrays: this many envs, drawn once from this seed
+
+
+def leaves(a, prefix=""):
+    """(name, array) of every leaf field of a structured array, padding bytes excluded."""
+    if a.dtype.names is None:
+        yield prefix, a
+        return
+    for nm in a.dtype.names:
+        yield from leaves(a[nm], prefix + "." + nm if prefix else nm)
+
+
+def dump_outputs(path, cg, d, env, smp):
+    """Write what the last timed step left, the arrays a caller of the rollout reads, as float32
+    <name>.npy under `path`: rewards, dones, agent_selection and the sampled actions of every env of
+    this rank, and the ObsData / selected ActionMask / Info records of DUMP_ENVS envs (a fixed sample
+    drawn from DUMP_SEED, listed in env_index.npy; 1.1 GB of ObsData otherwise).  A record array is
+    one row per env, its leaf fields in declaration order, padding left out."""
+    import numpy as np
+    n = env.rewards.shape[0]
+    env.sync_host()                                        # device views -> the host arrays
+    acts = d.torch.from_dlpack(smp.dlpack()).cpu().numpy().view(cg._city_of_gold.ActionData).reshape(n)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, min(n, DUMP_ENVS), replace=False))
+
+    def rows(a):
+        return np.concatenate([x.reshape(x.shape[0], -1).astype(np.float32) for _, x in leaves(a)], axis=1)
+
+    out = {"env_index": idx.astype(np.float32),
+           "observations": rows(env.observations[idx]),
+           "selected_action_masks": rows(env.selected_action_masks[idx]),
+           "infos": rows(env.infos[idx]),
+           "rewards": rows(env.rewards), "dones": rows(env.dones),
+           "agent_selection": rows(env.agent_selection), "actions": rows(acts)}
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
+
+
 def main():
     args = parse()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     d = Dist(args.gpus)
     import city_of_gold as cg
     from city_of_gold.shard import shard
@@ -596,20 +647,37 @@ def main():
     total_env_steps = d.sum(float(n) * args.steps)
     value = total_env_steps / wall_max
 
-    # ---- roofline of the dominant kernel at the timed launch length -----------------------
-    k_chunk = min(chunk, args.steps)
-    launch_s = kernel_time(runner, k_chunk, max(3, min(20, 4000 // max(k_chunk, 1))))
-    prof = load_profile()
-    roof = roofline(prof, n, k_chunk, launch_s, cg._city_of_gold.rollout_kind(n, N_PLAYERS, False), load_stamps(),
-                    load_stamps("issue_profile.json"))
+    dumped = None
+    if args.dump_outputs:                                  # the state the K timed steps left
+        dumped = dump_outputs(args.dump_outputs if d.world == 1 else
+                              os.path.join(args.dump_outputs, "rank%d" % d.rank), cg, d, env, smp)
 
-    haz, per = env.hazards()
-    n_erase = int(((per & HAZ_ERASE_PAST) != 0).sum())
-    n_any = int((per != 0).sum())
-    n_erase, n_any = int(d.sum(n_erase)), int(d.sum(n_any))
+    roof = parity = None
+    if args.full:
+        # ---- roofline of the dominant kernel at the timed launch length -------------------
+        k_chunk = min(chunk, args.steps)
+        launch_s = kernel_time(runner, k_chunk, max(3, min(20, 4000 // max(k_chunk, 1))))
+        prof = load_profile()
+        roof = roofline(prof, n, k_chunk, launch_s, cg._city_of_gold.rollout_kind(n, N_PLAYERS, False),
+                        load_stamps(), load_stamps("issue_profile.json"))
+
+        haz, per = env.hazards()
+        n_erase = int(((per & HAZ_ERASE_PAST) != 0).sum())
+        n_any = int((per != 0).sum())
+        n_erase, n_any = int(d.sum(n_erase)), int(d.sum(n_any))
+        parity = {"hazard_envs": n_any, "erase_past_envs": n_erase,
+                  "reference_pinned_envs": int(total_env_steps / max(args.steps, 1)) - n_any,
+                  "note": "tests/test_gpu_timed_workloads.py runs this workload (and each N's last "
+                          "shard) for 1,205 steps and compares every env with the C oracle; the "
+                          "reference_pinned_envs (every env without a hazard flag) are also compared "
+                          "with final-state digests the unmodified reference core produced "
+                          "(tests/golden/ref_workloads.npz). The hazard envs -- chiefly erase_past: "
+                          "map.cpp:727's past-the-end erase, GCC>=13 libstdc++ semantics, which a "
+                          "reference built against libstdc++ 11 cannot run -- are pinned by the C oracle "
+                          "only (DESIGN.md 3)"}
 
     extras = {}
-    if d.world == 1 and not args.no_extras:
+    if args.full and d.world == 1 and not args.no_extras:
         runner.set_chunk(chunk)
         extras["shard_sizes"] = {"us_per_step_at_%d" % n: launch_s / k_chunk * 1e6 if k_chunk >= 1000 else
                                  us_per_step(cg, n, dev),
@@ -731,7 +799,7 @@ def main():
 
     if d.rank == 0:
         cpu = None
-        if d.world == 1 and not args.no_cpu_baseline:
+        if args.full and d.world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.cpu_seconds)
             g = extras.get("asv_grid")
             if g:                                          # the crossover N against the same baseline
@@ -764,16 +832,10 @@ def main():
                 "seed": SEED,
                 "parallelism": f"env-sharded x{d.world} by index (runner.h:33-38 block split), no collectives",
             },
+            "full": args.full,
             "roofline": roof,
-            "parity": {"hazard_envs": n_any, "erase_past_envs": n_erase,
-                       "reference_pinned_envs": int(total_env_steps / max(args.steps, 1)) - n_any,
-                       "note": "tests/test_gpu_timed_workloads.py runs this workload (and each N's last "
-                               "shard) for 1,205 steps and compares every env with the C oracle; the "
-                               "reference_pinned_envs (every env without a hazard flag) are also compared "
-                               "with final-state digests the unmodified reference core produced "
-                               "(tests/golden/ref_workloads.npz). The hazard envs -- chiefly erase_past: "
-                               "map.cpp:727's past-the-end erase, GCC>=13 libstdc++ semantics, which the "
-                               "image's libstdc++ 11 cannot run -- are pinned by the C oracle only (DESIGN.md 3)"},
+            "parity": parity,
+            "dumped_outputs": dumped,
             "timing": "per rank: clock started after barrier + synchronize, stopped after the rank's own "
                       "torch.cuda.synchronize(); value uses the max over ranks; the closing barrier runs "
                       "after the clock",

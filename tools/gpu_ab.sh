@@ -13,7 +13,7 @@ for rep in 1 2 3; do
   timeout -k 10 120 tools/bin/$BASE base 65536 8192 >> "$OUT/probe.txt" 2>&1 || exit 1
 done
 PROBE_CHUNK=20 timeout -k 10 120 tools/bin/duoprobe_st trio 65536 > "$OUT/stamps_65536.txt" 2>&1 || exit 1
-timeout -k 10 120 python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err"
+timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err"
 rc=$?
 cat "$OUT/probe.txt"
 grep -A6 "launch timeline" "$OUT/stamps_65536.txt"

@@ -10,8 +10,8 @@ export TMPDIR=/tmp
 K=()
 [ -n "$2" ] && K=(-k "$2")
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread "${K[@]}" > "$OUT/tests.log" 2>&1 && \
-timeout -k 10 120 python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err" && \
-timeout -k 10 120 python bench.py --envs-total 8192 --steps 20 --warmup 5 --no-extras --no-cpu-baseline \
+timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err" && \
+timeout -k 10 120 python bench.py --full --envs-total 8192 --steps 20 --warmup 5 --no-extras --no-cpu-baseline \
     > "$OUT/shape_8192.json" 2> "$OUT/shape_8192.err" && \
 for rep in 1 2; do
   timeout -k 10 120 tools/bin/duoprobe trio 65536 8192 >> "$OUT/probe.txt" 2>&1 || exit 1

@@ -6,7 +6,7 @@
 #   2. s_memtime phase stamps of the stepping wave at the same shapes -> stamps_profile.json
 #      (bench.py's roofline.limiter; tools/stamps_profile.py), and the lone-wave instruction
 #      costs (tools/chainprobe.hip -> chainprobe.txt: roofline.limiter.issue_frac)
-#   3. GPU tests, smoke, the default bench (all extras + CPU baseline), the driver's shape, the
+#   3. GPU tests, smoke, bench.py --full (all extras + CPU baseline), the driver's shape, the
 #      N = 2, 4, 8 shard shapes, rocprofv3 kernel stats of the driver's shape
 # Then, in the container: copy pmc_profile.json and stamps_profile.json into profiles/, and run
 # python tools/issue_frac.py --chain gpurun_out/TAG/chainprobe.txt --json profiles/issue_profile.json
@@ -32,14 +32,14 @@ cp "$OUT/stamps_profile.json" profiles/stamps_profile.json && \
 timeout -k 10 60 tools/bin/chainprobe > "$OUT/chainprobe.txt" 2>&1 && \
 timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 600 --timeout-method thread > "$OUT/tests.log" 2>&1 && \
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 && \
-timeout -k 10 500 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" && \
-timeout -k 10 120 python bench.py --steps 20 --warmup 5 > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err" && \
+timeout -k 10 500 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" && \
+timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err" && \
 for n in 32768 16384 8192; do
-  timeout -k 10 120 python bench.py --envs-total $n --steps 20 --warmup 5 --no-extras --no-cpu-baseline \
+  timeout -k 10 120 python bench.py --full --envs-total $n --steps 20 --warmup 5 --no-extras --no-cpu-baseline \
       > "$OUT/shape_$n.json" 2> "$OUT/shape_$n.err" || exit 1
 done && \
 (cd /tmp && timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof" -o drv \
-   -- python3 "$OLDPWD/bench.py" --steps 20 --warmup 5 --no-extras --no-cpu-baseline) > "$OUT/prof.log" 2>&1
+   -- python3 "$OLDPWD/bench.py" --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline) > "$OUT/prof.log" 2>&1
 rc=$?
 tail -n 3 "$OUT/tests.log"
 tail -n 2 "$OUT/smoke.log"

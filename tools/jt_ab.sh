@@ -9,9 +9,9 @@ line() { python -c "import json,sys;d=json.loads(open('$1').read().strip().split
 for r in 1 2; do
   for jt in def 1 w3; do
     E=(); [ $jt = 1 ] && E=(env COG_TRIO_JT=1); [ $jt = w3 ] && E=(env COG_TRIO_WPC=3)
-    timeout -k 10 120 "${E[@]}" python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/d_$jt.json 2>/dev/null || exit 1
+    timeout -k 10 120 "${E[@]}" python bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline > $O/d_$jt.json 2>/dev/null || exit 1
     line $O/d_$jt.json "jt=$jt 20-step " >> $O/ab.txt
-    timeout -k 10 120 "${E[@]}" python bench.py --steps 2000 --warmup 200 --no-extras --no-cpu-baseline > $O/k_$jt.json 2>/dev/null || exit 1
+    timeout -k 10 120 "${E[@]}" python bench.py --full --steps 2000 --warmup 200 --no-extras --no-cpu-baseline > $O/k_$jt.json 2>/dev/null || exit 1
     line $O/k_$jt.json "jt=$jt 1000-step" >> $O/ab.txt
   done
 done
