@@ -32,8 +32,8 @@ LIB = os.path.join(OUT, "libcog_hip.so")
 LIB_FENCE = os.path.join(OUT, "libcog_hip_fence.so")
 EXT = os.path.join(OUT, "_city_of_gold" + sysconfig.get_config_var("EXT_SUFFIX"))
 
-ENGINE_SRCS = [os.path.join(CSRC, f) for f in ("cog_engine.hip", "cog_abi.cpp")]
-ENGINE_DEPS = ENGINE_SRCS + [os.path.join(CSRC, f) for f in ("cog_engine.h", "cog_tables.h", "cog_rng.h")] + [
+ENGINE_SRCS = [os.path.join(CSRC, f) for f in ("cog_engine.hip", "cog_abi.cpp", "cog_policy.hip")]
+ENGINE_DEPS = ENGINE_SRCS + [os.path.join(CSRC, f) for f in ("cog_engine.h", "cog_policy.h", "cog_tables.h", "cog_rng.h")] + [
     os.path.join(INCLUDE, f) for f in ("cog.h", "cog_types.h")]
 EXT_SRCS = [os.path.join(CSRC, "pybind_module.cpp")]
 
@@ -51,7 +51,7 @@ def _run(cmd, cwd=None):
 
 
 OBJ = os.path.join(PKG, "build")
-HEADERS = [os.path.join(CSRC, f) for f in ("cog_engine.h", "cog_tables.h", "cog_rng.h")] + [
+HEADERS = [os.path.join(CSRC, f) for f in ("cog_engine.h", "cog_policy.h", "cog_tables.h", "cog_rng.h")] + [
     os.path.join(INCLUDE, f) for f in ("cog.h", "cog_types.h")]
 
 
@@ -86,8 +86,8 @@ def build_engine(force=False, fence=True):
         raise subprocess.CalledProcessError(1, "hipcc")
     if force or _stale(LIB, objs):
         _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, "-o", LIB])
-    if fence and (force or _stale(LIB_FENCE, [eng_fence, objs[1]])):
-        _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", eng_fence, objs[1], "-o", LIB_FENCE])
+    if fence and (force or _stale(LIB_FENCE, [eng_fence] + objs[1:])):
+        _run([HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", eng_fence, *objs[1:], "-o", LIB_FENCE])
     return LIB
 
 

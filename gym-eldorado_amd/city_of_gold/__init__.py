@@ -14,7 +14,9 @@ N in {0..8, 16, 32, ..., 256}); input arrays are length/record-size checked (Val
 of an out-of-bounds read); views keep their owner alive.  Runners accept two extra keyword
 arguments: device_views=True keeps outputs in HBM (no per-sync host copy) and
 stored_masks=True samples from the current agent's stored mask (full game dynamics); samplers
-accept first_index= for a rank's block of a larger batch (city_of_gold.shard).
+accept first_index= for a rank's block of a larger batch (city_of_gold.shard), and have
+sample_policy(logits, envs, masks): masked categorical actions, their joint log-probability and
+entropy from a policy's logits on the GPU, feeding envs.step_device with no host round trip.
 
 All computation runs in libcog_hip.so on a gfx950 GPU.  There is no CPU fallback: creating an
 environment without a usable device raises RuntimeError.
@@ -103,7 +105,67 @@ def _make_sampler_cls(n):
         unwrapped, as in the whole batch (vec_sampler.h:9-13)."""
         _C.VecSamplerBase.__init__(self, n, seed, device, first_index)
 
+    def sample_policy(self, logits, envs=None, masks="selected", *, greedy=False, stream=None):
+        """Masked categorical actions from a policy's logits, one fused kernel on the GPU (an
+        addition: the reference samples uniformly only).
+
+        logits: torch tensor on the sampler's device, shape (n, 92) in ActionMask byte order (play
+        0..21, play_special 22..43, remove 44..65, move 66..72, get_from_shop 73..91), float32 or
+        bfloat16, stride(1) == 1, stride(0) >= 92.  masks: "selected" (envs' selected masks),
+        "stored" (the current agent's stored mask: full dynamics) or an (n, 128) uint8 device
+        tensor of ActionMask records.  greedy=True takes the valid entry with the largest logit and
+        leaves the sampler's state alone.  The kernel is ordered after `stream` (default: torch's
+        current stream on that device) and, with envs' masks, after the envs' queued work; what is
+        queued on that stream afterwards (reading the results, envs.step_device(actions)) runs
+        after it.  Nothing waits on the host.
+
+        Returns (actions, logp, entropy): the sampler's device actions, (n, 64) uint8, the memory
+        device_tensors(...)["actions"] aliases, and two new float32 (n,) tensors: the joint
+        log-probability of the five heads and their summed entropy (NaN for an env with a +inf
+        logit, or nothing but -inf / NaN, on a head's valid entries; its action is still legal)."""
+        import torch
+        if self.num_shards != 1:
+            raise ValueError(f"sample_policy of a {self.num_shards}-shard sampler: it needs a single-shard "
+                             "sampler (one device)")
+        if not isinstance(logits, torch.Tensor):
+            raise ValueError("sample_policy: logits must be a torch tensor")
+        dev = self.device
+        if logits.device.type != "cuda" or logits.device.index != dev:
+            raise ValueError(f"sample_policy: logits are on device {logits.device}, the sampler is on GPU {dev}")
+        if logits.dim() != 2 or tuple(logits.shape) != (n, 92):
+            raise ValueError(f"sample_policy: logits have shape {tuple(logits.shape)}, expected ({n}, 92)")
+        dtypes = {torch.float32: 0, torch.bfloat16: 1}
+        if logits.dtype not in dtypes:
+            raise ValueError(f"sample_policy: logits dtype {logits.dtype} is neither float32 nor bfloat16")
+        if n and (logits.stride(1) != 1 or (n > 1 and logits.stride(0) < 92)):
+            raise ValueError(f"sample_policy: logits strides {tuple(logits.stride())}: the inner stride must be 1 "
+                             "and the row stride at least 92")
+        ld = logits.stride(0) if n > 1 else 92
+        d_masks = 0
+        if isinstance(masks, str):
+            if masks not in ("selected", "stored"):
+                raise ValueError(f"sample_policy: masks {masks!r} is not 'selected', 'stored' or a tensor")
+            if envs is None:
+                raise ValueError(f"sample_policy: masks={masks!r} needs the envs whose masks they are (envs=None)")
+            source = 0 if masks == "selected" else 1
+        else:
+            if (not isinstance(masks, torch.Tensor) or masks.device != logits.device or masks.dtype != torch.uint8
+                    or tuple(masks.shape) != (n, 128) or not masks.is_contiguous()):
+                raise ValueError(f"sample_policy: mask records must be a contiguous ({n}, 128) uint8 tensor on "
+                                 "the logits' device")
+            source, envs, d_masks = 2, None, masks.data_ptr()
+        if stream is None:
+            stream = stream_handle(dev)
+        actions = torch.from_dlpack(self.dlpack())
+        logp = torch.empty(n, dtype=torch.float32, device=logits.device)
+        entropy = torch.empty(n, dtype=torch.float32, device=logits.device)
+        _C.VecSamplerBase.sample_policy_raw(self, logits.data_ptr(), dtypes[logits.dtype], ld, source, envs, d_masks,
+                                            logp.data_ptr(), entropy.data_ptr(), 1 if greedy else 0,
+                                            -1 if stream is None else int(stream))
+        return actions, logp, entropy
+
     return type(VEC_SAMPLER_CLS + str(n), (_C.VecSamplerBase,), {"__init__": __init__,
+                                                                 "sample_policy": sample_policy,
                                                                  "__module__": "city_of_gold.vec.env"})
 
 

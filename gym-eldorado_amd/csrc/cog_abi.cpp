@@ -31,6 +31,7 @@
 
 #include "../../include/cog.h"
 #include "cog_engine.h"
+#include "cog_policy.h"
 
 namespace {
 
@@ -325,6 +326,7 @@ struct SamplerShard {
   uint8_t *d_actions = nullptr;
   uint8_t *d_masks = nullptr;         // staging for host-provided masks
   Signal done;                        // completion word (cog_sampler::h_sig)
+  hipEvent_t ev = nullptr;            // cog_sampler_sample_policy on a caller's stream (created on first use)
 };
 
 // The speculative next sample (single-shard samplers and envs; cog::SampleSpec).  The reference's
@@ -669,6 +671,7 @@ void sampler_free(cog_sampler *s) {
     void *dev[] = {k.d_rng, k.d_actions, k.d_masks, k.done.ctr};
     for (void *p : dev)
       if (p) (void)hipFree(p);
+    if (k.ev) (void)hipEventDestroy(k.ev);
     if (k.stream) (void)hipStreamDestroy(k.stream);
   }
   zc_free(s->h_actions);
@@ -1321,6 +1324,79 @@ int cog_sampler_sample_device(cog_sampler *s, const void *d_masks, size_t n) {
   int rc = sampler_run(k, s->h_actions, static_cast<const uint8_t *>(d_masks), k.stream, true, true);
   if (rc || (rc = signal_enqueue(k.done, k.stream))) return rc;
   return signal_wait(k.done, k.stream);
+}
+
+// Masked categorical actions from a batch of logits (cog_policy.hip).  The kernel runs on the
+// caller's stream, so it follows the work that produced the logits and precedes whatever the caller
+// queues next (torch reading logp, cog_env_step_device_stream of the actions); the env's stream is
+// ordered around it by events when the masks are the env's records, and the sampler's own stream
+// after it, so later sampler calls see its state and actions.  Nothing here waits on the host.
+int cog_sampler_sample_policy(cog_sampler *s, const cog_policy_args *a) {
+  if (!s || !a) return fail(COG_ERR_INVALID, "NULL argument");
+  if (s->sh.size() != 1) return fail(COG_ERR_INVALID, "sample_policy needs a single-shard sampler (one device)");
+  if (!a->d_logits) return fail(COG_ERR_INVALID, "sample_policy: logits pointer is NULL");
+  if (a->logits_dtype != COG_LOGITS_F32 && a->logits_dtype != COG_LOGITS_BF16)
+    return fail(COG_ERR_INVALID, "sample_policy: unknown logits dtype " + std::to_string(a->logits_dtype));
+  if (a->ld < COG_MASK_USED)
+    return fail(COG_ERR_INVALID, "sample_policy: ld " + std::to_string(a->ld) + " < 92 logits per row");
+  const uintptr_t esz = a->logits_dtype == COG_LOGITS_BF16 ? 2 : 4;
+  if (reinterpret_cast<uintptr_t>(a->d_logits) % esz)
+    return fail(COG_ERR_INVALID, "sample_policy: logits pointer is not aligned to its element size");
+  SamplerShard &k = s->sh[0];
+  cog::PolicyLaunch p{};
+  EnvShard *ek = nullptr;
+  if (a->mask_source == COG_MASKS_SELECTED || a->mask_source == COG_MASKS_STORED) {
+    cog_env *env = a->env;
+    if (!env) return fail(COG_ERR_INVALID, "sample_policy: this mask source needs an env");
+    if (!single(env)) return fail(COG_ERR_INVALID, "sample_policy needs a single-shard env (one device)");
+    if (env->sh[0].device != k.device) return fail(COG_ERR_INVALID, "sample_policy: env and sampler are on different devices");
+    if (env->n != s->n) return fail(COG_ERR_INVALID, "sample_policy: env and sampler batch sizes differ");
+    ek = &env->sh[0];
+    if (a->mask_source == COG_MASKS_SELECTED) {
+      p.mask_base = ek->s.sel;
+      p.mask_stride = COG_MASK_BYTES;
+    } else {
+      p.mask_base = ek->s.obs + COG_OBS_PLAYER0 + COG_PD_MASK;
+      p.mask_stride = COG_OBS_BYTES;
+      p.agent = ek->s.agent;
+    }
+  } else if (a->mask_source == COG_MASKS_POINTER) {
+    if (!a->d_masks) return fail(COG_ERR_INVALID, "sample_policy: mask pointer is NULL");
+    if (reinterpret_cast<uintptr_t>(a->d_masks) % 16)
+      return fail(COG_ERR_INVALID, "sample_policy: mask records must be 16-byte aligned");
+    p.mask_base = static_cast<const uint8_t *>(a->d_masks);
+    p.mask_stride = COG_MASK_BYTES;
+  } else {
+    return fail(COG_ERR_INVALID, "sample_policy: unknown mask source " + std::to_string(a->mask_source));
+  }
+  s->version++;
+  s->spec.ok = false;                                      // a speculative uniform sample is stale now
+  s->exported = true;                                      // (the caller holds the device actions: no swaps)
+  if (!s->n) return COG_OK;
+  DeviceGuard g(k.device);
+  hipStream_t st = a->stream == COG_NO_STREAM ? k.stream : static_cast<hipStream_t>(a->stream);
+  if (ek) {                                                // after the env's queued work (its masks)
+    HIPCHK(hipEventRecord(ek->ev, ek->stream));
+    HIPCHK(hipStreamWaitEvent(st, ek->ev, 0));
+  }
+  p.n = s->n;
+  p.logits = a->d_logits;
+  p.bf16 = a->logits_dtype == COG_LOGITS_BF16;
+  p.ld = a->ld;
+  p.rng = k.d_rng;
+  p.actions = k.d_actions;
+  p.logp = a->d_logp;
+  p.entropy = a->d_entropy;
+  p.greedy = (a->flags & COG_POLICY_GREEDY) != 0;
+  if (cog::launch_policy_sample(p, st))
+    return fail(COG_ERR_HIP, std::string("policy sample launch failed: ") + hipGetErrorString(hipGetLastError()));
+  if (st != k.stream || ek) {                              // the sampler's (and the env's) later work after it
+    if (!k.ev) HIPCHK(hipEventCreateWithFlags(&k.ev, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(k.ev, st));
+    if (st != k.stream) HIPCHK(hipStreamWaitEvent(k.stream, k.ev, 0));
+    if (ek) HIPCHK(hipStreamWaitEvent(ek->stream, k.ev, 0));
+  }
+  return COG_OK;
 }
 
 int cog_sampler_sample(cog_sampler *s, const cog_action_mask_t *masks, size_t n) {

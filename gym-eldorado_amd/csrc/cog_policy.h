@@ -1,0 +1,30 @@
+// cog_policy.h -- internal interface between the C-ABI layer (cog_abi.cpp) and the policy sampler
+// kernel (cog_policy.hip): masked categorical actions from a batch of logits.  Not part of the
+// public ABI (include/cog.h cog_sampler_sample_policy is).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace cog {
+
+struct PolicyLaunch {
+  size_t n;                          // envs
+  const void *logits;                // [n] rows of >= 92 float32 / bfloat16 in ActionMask byte order
+  int bf16;                          // 0: float32, 1: bfloat16
+  size_t ld;                         // row stride in elements (>= 92)
+  // env i's ActionMask record is mask_base + i * mask_stride + (agent ? agent[i] * 256 : 0), 16-B aligned:
+  // the selected masks (stride 128), a caller's records (128), or the ObsData records' stored masks
+  // (mask_base = obs + 16192 + 128, stride 17216, agent = the env's agent_selection bytes)
+  const uint8_t *mask_base;
+  size_t mask_stride;
+  const uint8_t *agent;
+  uint32_t *rng;                     // [n] the sampler's minstd_rand0 states (untouched when greedy)
+  uint8_t *actions;                  // [n] ActionData records: the first 8 bytes of each are written
+  float *logp, *entropy;             // [n] each, or null
+  int greedy;
+};
+
+// 0, or -1 when the launch failed (hipGetLastError has the cause); n == 0 launches nothing
+int launch_policy_sample(const PolicyLaunch &p, void *stream);
+
+}  // namespace cog

@@ -1,0 +1,323 @@
+// cog_policy.hip -- the policy sampler (include/cog.h cog_sampler_sample_policy): one kernel from a
+// batch of logits and the envs' ActionMask records to ActionData records, the joint log-probability
+// and the entropy of the five masked categorical heads.
+//
+// Shape: one workgroup of four waves per tile of 64 envs.  The kernel is bandwidth-shaped (368 B of
+// float32 logits and 96 of the 128 mask bytes read per env, 16 B written), but the work per env is
+// a serial scan of 92 entries, so the tile goes through LDS once: the workgroup loads the tile's
+// rows with coalesced 16-B loads (consecutive lanes read consecutive granules of a row; with
+// ld == 92 the whole tile is one contiguous block), widens bfloat16 to float32 and stores the
+// values at an odd dword row stride (93: lane r reading column c of its own row hits bank
+// (93 r + c) mod 32, conflict-free).  The mask bytes are loaded the same way, 6 granules per env,
+// and kept as 92 bits per env.  Then lane r of every wave scans row r, each wave its share of the
+// heads, with the head's entries in registers (every loop is unrolled over the head's compile-time
+// size).  23.25 KiB of rows + 768 B of mask bits + 2.25 KiB of the waves' terms = 26.25 KiB of LDS
+// per workgroup: six workgroups (24 waves) share a CU.  The same kernel with one wave per tile doing
+// all five heads took twice the time (profiles/policy_sample_time.txt).
+//
+// Semantics (exact up to float32 rounding; tests/test_gpu_policy_sampler.py holds the numpy form):
+// per head, over the valid entries (mask byte != 0; a NaN logit counts as -inf): m = max l,
+// w_j = exp(l_j - m), Z = sum w, C_j the inclusive prefix sum; the action is the smallest j with
+// C_j > u Z (the last valid j when rounding leaves none), u = ((x_h - 1) >> 7) 2^-24 from the
+// sampler's minstd_rand0 state advanced once per head; logp += (l_j - m) - log Z,
+// entropy += log Z - sum w_j (l_j - m) / Z.  An empty head gives 0 and contributes nothing.  A head
+// whose valid entries hold +inf, or nothing but -inf / NaN, takes the greedy choice (largest logit,
+// lowest index) and makes the env's logp and entropy NaN.  Greedy mode takes that choice for every
+// head and leaves the sampler's state alone.
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+
+#include "../../include/cog_types.h"
+#include "cog_policy.h"
+#include "cog_rng.h"
+
+namespace cog {
+namespace {
+
+#define DEV __device__ __forceinline__
+
+constexpr int kTile = 64;                                  // envs per workgroup
+constexpr int kWaves = 4;                                  // waves per workgroup
+constexpr int kCols = COG_MASK_USED;                       // 92
+constexpr int kQuads = kCols / 4;                          // 23 groups of four logits per row
+constexpr int kRowStride = kCols + 1;                      // dwords per staged row (odd)
+static_assert(kCols % 4 == 0, "rows are whole groups of four logits");
+static_assert(COG_MASK_PLAY == 0 && COG_MASK_SPECIAL == 22 && COG_MASK_REMOVE == 44 && COG_MASK_MOVE == 66 &&
+                  COG_MASK_SHOP == 73 && COG_MASK_USED == 92,
+              "head offsets");
+
+DEV float bf16_widen(uint32_t h) { return __uint_as_float(h << 16); }
+
+// one bit per non-zero byte of w, bit k for byte k
+DEV uint32_t nonzero_bytes(uint32_t w) {
+  const uint32_t t = (((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) & 0x80808080u;
+  return (((t >> 7) * 0x00204081u) >> 21) & 0xfu;
+}
+
+DEV void put4(float *tile, int row, int col, float a, float b, float c, float d) {
+  float *p = tile + row * kRowStride + col;
+  p[0] = a;
+  p[1] = b;
+  p[2] = c;
+  p[3] = d;
+}
+DEV void put4_bf16(float *tile, int quad, uint32_t lo, uint32_t hi) {   // quad: row * 23 + group
+  put4(tile, quad / kQuads, 4 * (quad % kQuads), bf16_widen(lo & 0xffffu), bf16_widen(lo >> 16), bf16_widen(hi & 0xffffu),
+       bf16_widen(hi >> 16));
+}
+
+// rows [base, base + rows) of the logits into the tile, by the T threads of the workgroup.  VEC:
+// 16-B loads (the launcher has checked the alignment: float32 ld % 4 == 0; bfloat16 ld == 92 or
+// ld % 8 == 0; base pointer 16-B aligned)
+template <bool BF16, bool VEC, int T>
+DEV void stage_logits(float *tile, const void *logits, size_t ld, size_t base, int rows, int tid) {
+  if (!VEC) {
+#pragma unroll 4
+    for (int k = 0; k < (kTile * kCols + T - 1) / T; k++) {
+      const int q = k * T + tid, row = q / kCols, col = q % kCols;
+      if (row < rows) {
+        const size_t e = (base + row) * ld + col;
+        tile[row * kRowStride + col] =
+            BF16 ? bf16_widen(static_cast<const uint16_t *>(logits)[e]) : static_cast<const float *>(logits)[e];
+      }
+    }
+  } else if (!BF16) {
+    const float *L = static_cast<const float *>(logits);
+#pragma unroll
+    for (int k = 0; k < (kTile * kQuads + T - 1) / T; k++) {
+      const int q = k * T + tid, row = q / kQuads, col = 4 * (q % kQuads);
+      if (row < rows) {
+        const float4 v = *reinterpret_cast<const float4 *>(L + (base + row) * ld + col);
+        put4(tile, row, col, v.x, v.y, v.z, v.w);
+      }
+    }
+  } else if (ld == (size_t)kCols) {
+    // the tile is one contiguous block of rows x 23 quads of 8 B; a 16-B granule holds two quads
+    // (of two rows at a row's end), and the block's last granule may be half of one
+    const uint16_t *L = static_cast<const uint16_t *>(logits) + base * kCols;
+    const int total = rows * kQuads;
+#pragma unroll
+    for (int k = 0; k < (kTile * kQuads / 2 + T - 1) / T; k++) {
+      const int p = k * T + tid, g = 2 * p;
+      if (g + 1 < total) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(L + 8 * (size_t)p);
+        put4_bf16(tile, g, v.x, v.y);
+        put4_bf16(tile, g + 1, v.z, v.w);
+      } else if (g < total) {
+        const uint2 v = *reinterpret_cast<const uint2 *>(L + 8 * (size_t)p);
+        put4_bf16(tile, g, v.x, v.y);
+      }
+    }
+  } else {
+    // 16-B aligned rows: 11 granules and one half granule per row (columns 92.. are never read)
+    const uint16_t *L = static_cast<const uint16_t *>(logits);
+#pragma unroll
+    for (int k = 0; k < (kTile * 12 + T - 1) / T; k++) {
+      const int p = k * T + tid, row = p / 12, pc = p % 12;
+      if (row < rows) {
+        const uint16_t *src = L + (base + row) * ld + 8 * pc;
+        if (pc < 11) {
+          const uint4 v = *reinterpret_cast<const uint4 *>(src);
+          put4_bf16(tile, row * kQuads + 2 * pc, v.x, v.y);
+          put4_bf16(tile, row * kQuads + 2 * pc + 1, v.z, v.w);
+        } else {
+          const uint2 v = *reinterpret_cast<const uint2 *>(src);
+          put4_bf16(tile, row * kQuads + 22, v.x, v.y);
+        }
+      }
+    }
+  }
+}
+
+// One head of K entries at column OFF of the lane's staged row; vb: its valid bits.  Returns the
+// action; adds the head's terms to logp / ent, or sets bad for a degenerate head.
+template <int OFF, int K, bool GREEDY>
+DEV uint32_t sample_head(const float *row, uint32_t vb, float u, float &logp, float &ent, bool &bad) {
+  if (vb == 0u) return 0u;
+  float lv[K];
+  float m = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    const float x = row[OFF + j];
+    lv[j] = ((vb >> j) & 1u) && x == x ? x : -INFINITY;
+    m = fmaxf(m, lv[j]);
+  }
+  const bool degen = !(fabsf(m) < INFINITY);               // +inf, or nothing above -inf
+  uint32_t a = 0;
+  if (GREEDY || degen) {
+    uint32_t eq = 0;
+#pragma unroll
+    for (int j = 0; j < K; j++) eq |= (lv[j] == m ? 1u : 0u) << j;
+    a = (uint32_t)__ffs((int)(eq & vb)) - 1u;              // (invalid entries are -inf too: masked)
+  }
+  if (degen) {
+    bad = true;
+    return a;
+  }
+  float Z = 0.0f, S = 0.0f;
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    const float d = fmaxf(lv[j] - m, -3.0e38f);            // (finite: 0 * d is 0 for a masked entry)
+    const float w = __expf(d);
+    lv[j] = w;
+    Z += w;
+    S += w * d;
+  }
+  float da = 0.0f;                                         // l_a - m (greedy: the maximum itself)
+  if (!GREEDY) {
+    const float t = u * Z;
+    float C = 0.0f;
+    uint32_t below = 0;                                    // C is non-decreasing: the first j with C_j > t
+#pragma unroll                                             // is the number of j with C_j <= t, and its
+    for (int j = 0; j < K; j++) {                          // w_j > 0, so it is a valid entry
+      C += lv[j];
+      below += C <= t ? 1u : 0u;
+    }
+    a = below < (uint32_t)K ? below : 31u - (uint32_t)__clz((int)vb);
+    const float x = row[OFF + a];
+    da = x == x ? x - m : -INFINITY;
+  }
+  const float logZ = logf(Z);
+  logp += da - logZ;
+  ent += logZ - S / Z;
+  return a;
+}
+
+struct PolicyArgs {
+  size_t n;
+  const void *logits;
+  size_t ld;
+  const uint8_t *mask_base;
+  size_t mask_stride;
+  const uint8_t *agent;
+  uint32_t *rng;
+  uint8_t *actions;
+  float *logp, *entropy;
+};
+
+// Four waves stage the tile together and split the heads (play | play_special | remove | move +
+// get_from_shop: 22, 22, 22, 26 entries), lane r of each wave on env r; waves 1..3 leave their terms
+// in LDS and wave 0 adds them up and stores.
+template <bool BF16, bool VEC, bool GREEDY>
+__global__ void __launch_bounds__(kTile *kWaves) k_policy_sample(PolicyArgs a) {
+  constexpr int WAVES = kWaves;
+  __shared__ float tile[kTile * kRowStride];
+  __shared__ uint32_t mbits[kTile * 3];                    // 96 valid bits per env
+  __shared__ float part[(WAVES - 1) * 3 * kTile];          // waves 1..3: logp, entropy, actions | bad << 31
+  constexpr int T = kTile * WAVES;
+  const int tid = (int)threadIdx.x, lane = tid & (kTile - 1), wave = tid / kTile;
+  const size_t base = (size_t)blockIdx.x * kTile;
+  const int rows = a.n - base < (size_t)kTile ? (int)(a.n - base) : kTile;
+  const size_t i = base + lane;
+  const bool live = lane < rows;
+
+  float u[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  uint32_t x_new = 0;
+  if (!GREEDY && live) {                                   // one draw per head, as independent products
+    const uint32_t x = a.rng[i];                           // (read by every wave before the barrier; wave 0
+    constexpr uint32_t c[5] = {mr_pow(1), mr_pow(2), mr_pow(3), mr_pow(4), mr_pow(5)};   // writes after it)
+#pragma unroll
+    for (int h = 0; h < 5; h++) {
+      x_new = mr_jump(x, c[h]);
+      u[h] = (float)((x_new - 1u) >> 7) * (1.0f / 16777216.0f);
+    }
+  }
+  // the mask records: granule cc (of 6) of row `row`, 16 bits each
+#pragma unroll
+  for (int k = 0; k < (kTile * 6 + T - 1) / T; k++) {
+    const int q = k * T + tid, row = q / 6, cc = q % 6;
+    if (q < kTile * 6) {
+      uint32_t bits = 0;
+      if (row < rows) {
+        const size_t e = base + row;
+        const uint8_t *rec = a.mask_base + e * a.mask_stride;
+        if (a.agent) rec += (size_t)(a.agent[e] & 3u) * COG_OBS_PLAYER_STRIDE;
+        const uint4 v = reinterpret_cast<const uint4 *>(rec)[cc];
+        bits = nonzero_bytes(v.x) | nonzero_bytes(v.y) << 4 | nonzero_bytes(v.z) << 8 | nonzero_bytes(v.w) << 12;
+      }
+      reinterpret_cast<uint16_t *>(mbits)[q] = (uint16_t)bits;
+    }
+  }
+  stage_logits<BF16, VEC, T>(tile, a.logits, a.ld, base, rows, tid);
+  __syncthreads();
+
+  float logp = 0.0f, ent = 0.0f;
+  bool bad = false;
+  uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0;
+  if (live) {
+    const float *row = tile + lane * kRowStride;
+    const uint64_t lo = (uint64_t)mbits[3 * lane] | (uint64_t)mbits[3 * lane + 1] << 32;       // bits 0..63
+    const uint64_t hi = (uint64_t)mbits[3 * lane + 1] | (uint64_t)mbits[3 * lane + 2] << 32;   // bits 32..95
+    if (wave == 0)
+      a0 = sample_head<COG_MASK_PLAY, 22, GREEDY>(row, (uint32_t)(lo >> COG_MASK_PLAY) & 0x3fffffu, u[0], logp, ent, bad);
+    if (wave == 1)
+      a1 = sample_head<COG_MASK_SPECIAL, 22, GREEDY>(row, (uint32_t)(lo >> COG_MASK_SPECIAL) & 0x3fffffu, u[1], logp, ent, bad);
+    if (wave == 2)
+      a2 = sample_head<COG_MASK_REMOVE, 22, GREEDY>(row, (uint32_t)(hi >> (COG_MASK_REMOVE - 32)) & 0x3fffffu, u[2], logp, ent,
+                                                    bad);
+    if (wave == 3) {
+      a3 = sample_head<COG_MASK_MOVE, 7, GREEDY>(row, (uint32_t)(hi >> (COG_MASK_MOVE - 32)) & 0x7fu, u[3], logp, ent, bad);
+      a4 = sample_head<COG_MASK_SHOP, 19, GREEDY>(row, (uint32_t)(hi >> (COG_MASK_SHOP - 32)) & 0x7ffffu, u[4], logp, ent, bad);
+    }
+  }
+  if (wave > 0) {
+    float *p = part + (wave - 1) * 3 * kTile + lane;
+    p[0] = logp;
+    p[kTile] = ent;
+    p[2 * kTile] = __uint_as_float(a1 | a2 | a3 | a4 << 8 | (bad ? 0x80000000u : 0u));
+  }
+  __syncthreads();
+  if (wave > 0 || !live) return;
+#pragma unroll
+  for (int w = 1; w < WAVES; w++) {
+    const float *p = part + (w - 1) * 3 * kTile + lane;
+    logp += p[0];
+    ent += p[kTile];
+    const uint32_t b = __float_as_uint(p[2 * kTile]);
+    bad = bad || (b >> 31) != 0u;
+    if (w == 1) a1 = b & 0xffu;
+    if (w == 2) a2 = b & 0xffu;
+    if (w == 3) {
+      a3 = b & 0xffu;
+      a4 = (b >> 8) & 0xffu;
+    }
+  }
+  if (!GREEDY) a.rng[i] = x_new;
+  // the 8 bytes the uniform sampler writes at the head of the record (play .. get_from_shop, zeros)
+  *reinterpret_cast<uint2 *>(a.actions + i * COG_ACTION_BYTES) = make_uint2(a0 | a1 << 8 | a2 << 16 | a3 << 24, a4);
+  if (a.logp) a.logp[i] = bad ? __uint_as_float(0x7fc00000u) : logp;
+  if (a.entropy) a.entropy[i] = bad ? __uint_as_float(0x7fc00000u) : ent;
+}
+
+template <bool BF16, bool VEC>
+void launch_form(const PolicyArgs &a, bool greedy, dim3 grid, hipStream_t st) {
+  if (greedy)
+    hipLaunchKernelGGL((k_policy_sample<BF16, VEC, true>), grid, dim3(kTile * kWaves), 0, st, a);
+  else
+    hipLaunchKernelGGL((k_policy_sample<BF16, VEC, false>), grid, dim3(kTile * kWaves), 0, st, a);
+}
+
+}  // namespace
+
+int launch_policy_sample(const PolicyLaunch &p, void *stream) {
+  if (!p.n) return 0;
+  const PolicyArgs a{p.n, p.logits, p.ld, p.mask_base, p.mask_stride, p.agent, p.rng, p.actions, p.logp, p.entropy};
+  const dim3 grid((unsigned)((p.n + kTile - 1) / kTile));
+  hipStream_t st = (hipStream_t)stream;
+  const bool aligned = (reinterpret_cast<uintptr_t>(p.logits) & 15u) == 0;
+  if (p.bf16) {
+    if (aligned && (p.ld == (size_t)kCols || p.ld % 8 == 0))
+      launch_form<true, true>(a, p.greedy != 0, grid, st);
+    else
+      launch_form<true, false>(a, p.greedy != 0, grid, st);
+  } else {
+    if (aligned && p.ld % 4 == 0)
+      launch_form<false, true>(a, p.greedy != 0, grid, st);
+    else
+      launch_form<false, false>(a, p.greedy != 0, grid, st);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace cog

@@ -493,6 +493,28 @@ PYBIND11_MODULE(_city_of_gold, m) {
         check(cog_sampler_num_shards(s.handle(), &k));
         return k;
       })
+      .def_property_readonly("device", [](VecSampler &s) { return cog_sampler_device(s.handle()); },
+                             "device ordinal (of shard 0)")
+      .def("sample_policy_raw", [](VecSampler &s, uintptr_t d_logits, int dtype, size_t ld, int mask_source,
+                                   const py::object &env, uintptr_t d_masks, uintptr_t d_logp, uintptr_t d_entropy,
+                                   uint32_t flags, int64_t stream) {
+        // cog_sampler_sample_policy over raw device pointers (city_of_gold sample_policy is the torch
+        // face): dtype 0 float32 / 1 bfloat16, mask_source 0 selected / 1 stored / 2 d_masks,
+        // flags 1 = greedy, stream a hipStream_t handle (0 = the null stream; -1: none)
+        cog_policy_args a{};
+        a.d_logits = reinterpret_cast<const void *>(d_logits);
+        a.logits_dtype = dtype;
+        a.ld = ld;
+        a.mask_source = mask_source;
+        a.env = env.is_none() ? nullptr : env.cast<VecEnv &>().handle();
+        a.d_masks = reinterpret_cast<const void *>(d_masks);
+        a.d_logp = reinterpret_cast<float *>(d_logp);
+        a.d_entropy = reinterpret_cast<float *>(d_entropy);
+        a.flags = flags;
+        a.stream = stream < 0 ? COG_NO_STREAM : reinterpret_cast<void *>((uintptr_t)stream);
+        check(cog_sampler_sample_policy(s.handle(), &a));
+      }, "d_logits"_a, "dtype"_a, "ld"_a, "mask_source"_a, "env"_a = py::none(), "d_masks"_a = 0, "d_logp"_a = 0,
+         "d_entropy"_a = 0, "flags"_a = 0, "stream"_a = -1)
       .def("dlpack", [](py::object self) {       // the device actions (ActionData rows), single shard
         VecSampler &s = self.cast<VecSampler &>();
         int k = 0;

@@ -151,10 +151,13 @@ COG_API int cog_env_signal_stream(cog_env *env, int shard, void *stream);
 /* after the caller wrote the env's device records (DLPack views / d_* pointers), ordered after
  * the work queued on `stream` so far (COG_NO_STREAM: none): the engine takes the records as they
  * now are, as the reference's views alias its live state (include/pybind/common.h:97-101) -- the
- * decks, phase, resources and shop are read from the records anyway; the selected and stored
- * ActionMask records (0/1 bytes) and Info steps_taken also feed the engine's private mirrors, which
- * this rebuilds.  Host views are refreshed when the env has them.  Without this call, writes to
- * those records are not seen by the next step (see INTEGRATION.md "Device views"). */
+ * phase, resources and shop are read from the records anyway, and so are the decks by every launch
+ * except a trio rollout that follows another one: that one starts from the compact deck image the
+ * last one left, so once a trio rollout has run, deck writes are taken only after this call; the
+ * selected and stored ActionMask records (0/1 bytes) and Info steps_taken also feed the engine's
+ * private mirrors, which this rebuilds.  Host views are refreshed when the env has them.  Without
+ * this call, writes to those records are not seen by the next step (see INTEGRATION.md "Device
+ * views"). */
 COG_API int cog_env_invalidate_device(cog_env *env, void *stream);
 /* diagnostics: re-run the map-observation encode (map.cpp:389-405) over all envs `iters`
  * times back to back; average device time per launch (HIP events).  Output is unchanged.
@@ -195,6 +198,37 @@ COG_API void cog_sampler_destroy(cog_sampler *s);
 COG_API int cog_sampler_sample(cog_sampler *s, const cog_action_mask_t *masks, size_t n);
 /* same, masks in device memory (e.g. an env's d_selected_action_masks); single-shard samplers */
 COG_API int cog_sampler_sample_device(cog_sampler *s, const void *d_masks, size_t n);
+/* Policy sampler (an addition: the reference samples uniformly only): masked categorical actions
+ * from a batch of logits in device memory, one fused kernel.  Row i holds 92 logits in ActionMask
+ * byte order (play 0..21, play_special 22..43, remove 44..65, move 66..72, get_from_shop 73..91),
+ * float32 or bfloat16 (widened exactly), rows `ld` elements apart (ld >= 92, any value).  A mask
+ * byte != 0 is valid.  Per head h = 0..4 the sampler's minstd_rand0 state advances once,
+ * u = ((x - 1) >> 7) * 2^-24, and over the valid entries in float32: m = max l, w_j = exp(l_j - m),
+ * Z = sum w, action = the smallest j whose inclusive prefix sum exceeds u * Z;
+ * logp += (l_j - m) - log Z, entropy += log Z - sum w_j (l_j - m) / Z.  A head with no valid entry
+ * gives 0 and contributes nothing.  COG_POLICY_GREEDY: the valid entry with the largest logit
+ * (NaN as -inf, ties to the lowest index), no draws, state untouched.  A head whose valid entries
+ * hold +inf, or nothing but -inf / NaN, takes the greedy choice and makes that env's logp and
+ * entropy NaN: an illegal action is never produced.
+ * Writes the first 8 bytes of each of the sampler's device ActionData records (as every sample
+ * does; cog_sampler_device_actions) and d_logp / d_entropy (n floats each; either may be NULL);
+ * the host actions view is not refreshed.  Single-shard samplers (and envs, on the same device,
+ * env->n == n) only.  The kernel is ordered after the work queued on `stream` so far and, with the
+ * env's masks, after the env's queued work; work queued later on `stream` runs after it.  The
+ * call does not wait on the host.  d_masks: 16-byte aligned. */
+#define COG_LOGITS_F32 0
+#define COG_LOGITS_BF16 1
+#define COG_MASKS_SELECTED 0   /* env's selected masks                */
+#define COG_MASKS_STORED 1     /* env's current agent's stored mask   */
+#define COG_MASKS_POINTER 2    /* d_masks: n ActionMask records        */
+#define COG_POLICY_GREEDY 0x1u
+typedef struct cog_policy_args {
+  const void *d_logits; int logits_dtype; size_t ld;
+  int mask_source; cog_env *env; const void *d_masks;
+  float *d_logp; float *d_entropy;      /* may be NULL */
+  uint32_t flags; void *stream;         /* caller's hipStream_t, or COG_NO_STREAM */
+} cog_policy_args;
+COG_API int cog_sampler_sample_policy(cog_sampler *s, const cog_policy_args *a);
 COG_API cog_action_t *cog_sampler_actions(cog_sampler *s);   /* persistent host view */
 COG_API void *cog_sampler_device_actions(cog_sampler *s);    /* device view (shard 0) */
 COG_API void *cog_sampler_shard_device_actions(cog_sampler *s, int shard);
