@@ -17,6 +17,9 @@ stored_masks=True samples from the current agent's stored mask (full game dynami
 accept first_index= for a rank's block of a larger batch (city_of_gold.shard), and have
 sample_policy(logits, envs, masks): masked categorical actions, their joint log-probability and
 entropy from a policy's logits on the GPU, feeding envs.step_device with no host round trip.
+For the update, policy_evaluate(logits, actions, masks) gives the log-probability of recorded
+actions and the entropy under new logits, with gradients (a torch.autograd.Function over two HIP
+kernels), and mask_records(envs, source) copies the masks a trainer has to record with them.
 
 All computation runs in libcog_hip.so on a gfx950 GPU.  There is no CPU fallback: creating an
 environment without a usable device raises RuntimeError.
@@ -229,6 +232,128 @@ def stream_handle(device=None):
     return None
 
 
+def mask_records(envs, source="selected"):
+    """A copy of the ActionMask records sample_policy(logits, envs, source) reads, as an (n, 128)
+    uint8 torch tensor on the envs' device: "selected", the envs' selected masks, or "stored", each
+    env's current agent's stored mask.  A trainer records them before sampling, to evaluate the taken
+    actions under new logits later (policy_evaluate).  The copy is taken on torch's current stream,
+    after the envs' queued work; single-shard envs only."""
+    import torch
+    if source not in ("selected", "stored"):
+        raise ValueError(f"mask_records: source {source!r} is not 'selected' or 'stored'")
+    if envs.num_shards != 1:
+        raise ValueError(f"mask_records of a {envs.num_shards}-shard env: it needs a single-shard env (one device)")
+    dev = envs.shard_info(0)[2]
+    with torch.cuda.device(dev):
+        envs.signal_stream(stream_handle(dev), 0)
+        if source == "selected":
+            return torch.from_dlpack(envs.dlpack("selected_action_masks", 0)).clone()
+        obs = torch.from_dlpack(envs.dlpack("observations", 0))             # (n, 17216) ObsData records
+        agent = torch.from_dlpack(envs.dlpack("agent_selection", 0)).long() & 3
+        # ObsData.player_data[agent].action_mask: byte 16192 + 256 agent + 128 of the record
+        cols = (16192 + 128 + 256 * agent)[:, None] + torch.arange(128, device=obs.device)
+        return obs.gather(1, cols)
+
+
+_policy_evaluate_fn = None
+_LOGITS_DTYPES = {"torch.float32": 0, "torch.bfloat16": 1}
+
+
+def _policy_evaluate_function():
+    """The torch.autograd.Function behind policy_evaluate (built on first use: torch is optional)."""
+    global _policy_evaluate_fn
+    if _policy_evaluate_fn is not None:
+        return _policy_evaluate_fn
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    def raw(logits, actions, masks, *, logp=None, entropy=None, g_lp=None, g_en=None, grad=None):
+        b = logits.shape[0]
+        ptr = lambda t: 0 if t is None else t.data_ptr()     # noqa: E731
+        dev = logits.device.index
+        _C.policy_evaluate_raw(b, logits.data_ptr(), _LOGITS_DTYPES[str(logits.dtype)],
+                               logits.stride(0) if b > 1 else 92, actions.data_ptr(),
+                               actions.stride(0) if b > 1 else actions.shape[1], masks.data_ptr(), ptr(logp),
+                               ptr(entropy), ptr(g_lp), ptr(g_en), ptr(grad), dev,
+                               int(torch.cuda.current_stream(dev).cuda_stream), grad is not None)
+
+    class PolicyEvaluate(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, logits, actions, masks):
+            b = logits.shape[0]
+            logp = torch.empty(b, dtype=torch.float32, device=logits.device)
+            entropy = torch.empty(b, dtype=torch.float32, device=logits.device)
+            raw(logits, actions, masks, logp=logp, entropy=entropy)
+            ctx.save_for_backward(logits, actions, masks)
+            ctx.set_materialize_grads(False)
+            return logp, entropy
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, g_lp, g_en):
+            logits, actions, masks = ctx.saved_tensors
+            g_lp, g_en = (None if g is None else g.to(torch.float32).contiguous() for g in (g_lp, g_en))
+            grad = torch.empty((logits.shape[0], 92), dtype=logits.dtype, device=logits.device)
+            raw(logits, actions, masks, g_lp=g_lp, g_en=g_en, grad=grad)
+            return grad, None, None
+
+    _policy_evaluate_fn = PolicyEvaluate
+    return PolicyEvaluate
+
+
+def policy_evaluate(logits, actions, masks):
+    """Joint log-probability of recorded actions and entropy of the five masked categorical heads
+    under new logits, differentiable with respect to the logits: the distribution sample_policy
+    draws from, for a trainer's update (ratio = exp(policy_evaluate(new_logits, a, m)[0] - old_logp)).
+    One HIP kernel forward, one backward, on torch's current stream.
+
+    logits: (B, 92) float32 or bfloat16 on a GPU in ActionMask byte order, stride(1) == 1,
+    stride(0) >= 92 (a view such as net_out[:, :92] of a wider layer is taken as is).  actions:
+    (B, k) uint8, k >= 5, stride(1) == 1, on the same device: bytes 0..4 of a row are play,
+    play_special, remove, move, get_from_shop (the (n, 64) tensor sample_policy returns, a clone of
+    it, or its [:, :5] columns in a rollout buffer).  masks: contiguous (B, 128) uint8 ActionMask
+    records on the same device (mask_records).  B is any size.  The backward reads the three
+    tensors again (nothing else is saved): the sampler's own action tensor, which the next
+    sample_policy call overwrites, has to be cloned to outlive that call.
+
+    Returns (logp, entropy), two float32 (B,) tensors.  A head with no valid entry contributes
+    nothing.  A row with a +inf logit, or nothing but -inf / NaN, on a non-empty head's valid
+    entries, or whose recorded action is not a valid entry, has NaN logp and entropy and an all-zero
+    gradient row.  Gradients flow to logits only; double backward is not supported."""
+    import torch
+    for name, t in (("logits", logits), ("actions", actions), ("masks", masks)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"policy_evaluate: {name} must be a torch tensor")
+    if logits.device.type != "cuda":
+        raise ValueError(f"policy_evaluate: logits are on device {logits.device}, not on a GPU")
+    if logits.dim() != 2 or logits.shape[1] != 92:
+        raise ValueError(f"policy_evaluate: logits have shape {tuple(logits.shape)}, expected (B, 92)")
+    b = logits.shape[0]
+    if str(logits.dtype) not in _LOGITS_DTYPES:
+        raise ValueError(f"policy_evaluate: logits dtype {logits.dtype} is neither float32 nor bfloat16")
+    if b and (logits.stride(1) != 1 or (b > 1 and logits.stride(0) < 92)):
+        raise ValueError(f"policy_evaluate: logits strides {tuple(logits.stride())}: the inner stride must be 1 "
+                         "and the row stride at least 92")
+    if actions.device != logits.device:
+        raise ValueError(f"policy_evaluate: actions are on device {actions.device}, the logits on {logits.device}")
+    if actions.dtype != torch.uint8:
+        raise ValueError(f"policy_evaluate: actions dtype {actions.dtype} is not uint8")
+    if actions.dim() != 2 or actions.shape[0] != b or actions.shape[1] < 5:
+        raise ValueError(f"policy_evaluate: actions have shape {tuple(actions.shape)}, expected ({b}, k) with k >= 5")
+    if b and (actions.stride(1) != 1 or (b > 1 and actions.stride(0) < 5)):
+        raise ValueError(f"policy_evaluate: actions strides {tuple(actions.stride())}: the inner stride must be 1 "
+                         "and the row stride at least 5")
+    if masks.device != logits.device:
+        raise ValueError(f"policy_evaluate: masks are on device {masks.device}, the logits on {logits.device}")
+    if masks.dtype != torch.uint8:
+        raise ValueError(f"policy_evaluate: masks dtype {masks.dtype} is not uint8")
+    if tuple(masks.shape) != (b, 128):
+        raise ValueError(f"policy_evaluate: masks have shape {tuple(masks.shape)}, expected ({b}, 128)")
+    if not masks.is_contiguous():
+        raise ValueError(f"policy_evaluate: masks strides {tuple(masks.stride())}: the records must be contiguous")
+    return _policy_evaluate_function().apply(logits, actions, masks)
+
+
 from .single import cog_env  # noqa: E402  (src/pybind/single_env.cpp: the single-env API)
 
 get_vec_env = _getter(vec.sampler, VEC_ENV_CLS, _make_env_cls)
@@ -243,4 +368,5 @@ del _n, _m
 
 __all__ = ["vec", "Difficulty", "EASY", "MEDIUM", "HARD", "ObsData", "ActionMask", "ActionData", "Info",
            "DeckObs", "SharedObservation", "PlayerData", "PlayerObservation", "action_sampler", "get_vec_env",
-           "get_vec_sampler", "get_runner", "device_count", "device_tensors", "stream_handle", "cog_env"]
+           "get_vec_sampler", "get_runner", "device_count", "device_tensors", "stream_handle", "cog_env", "policy_evaluate",
+           "mask_records"]

@@ -1399,6 +1399,60 @@ int cog_sampler_sample_policy(cog_sampler *s, const cog_policy_args *a) {
   return COG_OK;
 }
 
+// The policy evaluator (cog_policy.hip): no handle, no event, no host wait -- one kernel on the
+// caller's stream on the caller's device.
+static int policy_evaluate(const cog_policy_eval_args *a, bool backward) {
+  const char *who = backward ? "policy_evaluate_backward" : "policy_evaluate";
+  auto bad = [&](const std::string &msg) { return fail(COG_ERR_INVALID, std::string(who) + ": " + msg); };
+  if (!a) return fail(COG_ERR_INVALID, "NULL argument");
+  if (a->logits_dtype != COG_LOGITS_F32 && a->logits_dtype != COG_LOGITS_BF16)
+    return bad("unknown logits dtype " + std::to_string(a->logits_dtype));
+  if (a->ld < COG_MASK_USED) return bad("ld " + std::to_string(a->ld) + " < 92 logits per row");
+  if (a->action_stride < 5) return bad("action_stride " + std::to_string(a->action_stride) + " < 5 action bytes per row");
+  if (a->stream == COG_NO_STREAM) return bad("COG_NO_STREAM: it runs on the caller's stream (NULL is the null stream)");
+  if (a->device < 0) return bad("device ordinal " + std::to_string(a->device) + " out of range");
+  if (!a->n) return COG_OK;
+  if (!a->d_logits) return bad("logits pointer is NULL");
+  if (!a->d_actions) return bad("actions pointer is NULL");
+  if (!a->d_masks) return bad("mask pointer is NULL");
+  const uintptr_t esz = a->logits_dtype == COG_LOGITS_BF16 ? 2 : 4;
+  if (reinterpret_cast<uintptr_t>(a->d_logits) % esz) return bad("logits pointer is not aligned to its element size");
+  if (reinterpret_cast<uintptr_t>(a->d_masks) % 16) return bad("mask records must be 16-byte aligned");
+  cog::PolicyEval p{};
+  if (backward) {
+    if (!a->d_grad_logits) return bad("grad_logits pointer is NULL");
+    if (reinterpret_cast<uintptr_t>(a->d_grad_logits) % 16) return bad("grad_logits must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(a->d_grad_logp) % 4 || reinterpret_cast<uintptr_t>(a->d_grad_entropy) % 4)
+      return bad("grad_logp / grad_entropy pointer is not aligned to float");
+    p.g_logp = a->d_grad_logp;
+    p.g_entropy = a->d_grad_entropy;
+    p.grad = a->d_grad_logits;
+  } else {
+    if (reinterpret_cast<uintptr_t>(a->d_logp) % 4 || reinterpret_cast<uintptr_t>(a->d_entropy) % 4)
+      return bad("logp / entropy pointer is not aligned to float");
+    p.logp = a->d_logp;
+    p.entropy = a->d_entropy;
+  }
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
+    return fail(COG_ERR_NODEVICE, "no HIP device available (the engine has no CPU fallback)");
+  if (a->device >= count) return bad("device ordinal " + std::to_string(a->device) + " out of range");
+  p.n = a->n;
+  p.logits = a->d_logits;
+  p.bf16 = a->logits_dtype == COG_LOGITS_BF16;
+  p.ld = a->ld;
+  p.actions = a->d_actions;
+  p.action_stride = a->action_stride;
+  p.masks = static_cast<const uint8_t *>(a->d_masks);
+  DeviceGuard g(a->device);
+  if (cog::launch_policy_eval(p, backward, a->stream))
+    return fail(COG_ERR_HIP, std::string(who) + " launch failed: " + hipGetErrorString(hipGetLastError()));
+  return COG_OK;
+}
+
+int cog_policy_evaluate(const cog_policy_eval_args *a) { return policy_evaluate(a, false); }
+int cog_policy_evaluate_backward(const cog_policy_eval_args *a) { return policy_evaluate(a, true); }
+
 int cog_sampler_sample(cog_sampler *s, const cog_action_mask_t *masks, size_t n) {
   if (!s || (!masks && n)) return fail(COG_ERR_INVALID, "NULL argument");
   if (n != s->n) return fail(COG_ERR_INVALID, "action_mask length != num_envs");

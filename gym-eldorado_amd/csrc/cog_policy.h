@@ -1,6 +1,7 @@
 // cog_policy.h -- internal interface between the C-ABI layer (cog_abi.cpp) and the policy sampler
-// kernel (cog_policy.hip): masked categorical actions from a batch of logits.  Not part of the
-// public ABI (include/cog.h cog_sampler_sample_policy is).
+// kernels (cog_policy.hip): masked categorical actions from a batch of logits, and the evaluator of
+// recorded actions under new logits with its gradient.  Not part of the public ABI (include/cog.h
+// cog_sampler_sample_policy, cog_policy_evaluate and cog_policy_evaluate_backward are).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -26,5 +27,22 @@ struct PolicyLaunch {
 
 // 0, or -1 when the launch failed (hipGetLastError has the cause); n == 0 launches nothing
 int launch_policy_sample(const PolicyLaunch &p, void *stream);
+
+// the policy evaluator (include/cog.h cog_policy_evaluate / cog_policy_evaluate_backward)
+struct PolicyEval {
+  size_t n;                          // rows
+  const void *logits;                // as PolicyLaunch
+  int bf16;
+  size_t ld;
+  const uint8_t *actions;            // row i's recorded action bytes 0..4 at actions + i * action_stride
+  size_t action_stride;              // >= 5
+  const uint8_t *masks;              // [n] ActionMask records of 128 B, 16-B aligned
+  float *logp, *entropy;             // forward: [n] each, or null
+  const float *g_logp, *g_entropy;   // backward: [n] incoming gradients, null = zeros
+  void *grad;                        // backward: [n] contiguous rows of 92 in the logits' dtype, 16-B aligned
+};
+
+// the forward or the backward kernel; 0, or -1 when the launch failed; n == 0 launches nothing
+int launch_policy_eval(const PolicyEval &p, bool backward, void *stream);
 
 }  // namespace cog

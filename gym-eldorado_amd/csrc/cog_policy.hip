@@ -24,9 +24,14 @@
 // whose valid entries hold +inf, or nothing but -inf / NaN, takes the greedy choice (largest logit,
 // lowest index) and makes the env's logp and entropy NaN.  Greedy mode takes that choice for every
 // head and leaves the sampler's state alone.
+//
+// The policy evaluator (cog_policy_evaluate and its backward, further down) shares the staging code
+// and the shape.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
+
+#include <type_traits>
 
 #include "../../include/cog_types.h"
 #include "cog_policy.h"
@@ -130,6 +135,40 @@ DEV void stage_logits(float *tile, const void *logits, size_t ld, size_t base, i
   }
 }
 
+// the mask records of rows [base, base + rows) as 96 valid bits per row (mbits: 3 dwords a row; rows
+// past `rows` get zeros): granule cc (of 6) of row `row`, 16 bits each
+template <int T>
+DEV void stage_masks(uint32_t *mbits, const uint8_t *mask_base, size_t mask_stride, const uint8_t *agent, size_t base,
+                     int rows, int tid) {
+#pragma unroll
+  for (int k = 0; k < (kTile * 6 + T - 1) / T; k++) {
+    const int q = k * T + tid, row = q / 6, cc = q % 6;
+    if (q < kTile * 6) {
+      uint32_t bits = 0;
+      if (row < rows) {
+        const size_t e = base + row;
+        const uint8_t *rec = mask_base + e * mask_stride;
+        if (agent) rec += (size_t)(agent[e] & 3u) * COG_OBS_PLAYER_STRIDE;
+        const uint4 v = reinterpret_cast<const uint4 *>(rec)[cc];
+        bits = nonzero_bytes(v.x) | nonzero_bytes(v.y) << 4 | nonzero_bytes(v.z) << 8 | nonzero_bytes(v.w) << 12;
+      }
+      reinterpret_cast<uint16_t *>(mbits)[q] = (uint16_t)bits;
+    }
+  }
+}
+
+// the valid bits of row `lane`'s five heads
+struct HeadBits {
+  uint32_t play, special, remove, move, shop;
+};
+DEV HeadBits head_bits(const uint32_t *mbits, int lane) {
+  const uint64_t lo = (uint64_t)mbits[3 * lane] | (uint64_t)mbits[3 * lane + 1] << 32;       // bits 0..63
+  const uint64_t hi = (uint64_t)mbits[3 * lane + 1] | (uint64_t)mbits[3 * lane + 2] << 32;   // bits 32..95
+  return {(uint32_t)(lo >> COG_MASK_PLAY) & 0x3fffffu, (uint32_t)(lo >> COG_MASK_SPECIAL) & 0x3fffffu,
+          (uint32_t)(hi >> (COG_MASK_REMOVE - 32)) & 0x3fffffu, (uint32_t)(hi >> (COG_MASK_MOVE - 32)) & 0x7fu,
+          (uint32_t)(hi >> (COG_MASK_SHOP - 32)) & 0x7ffffu};
+}
+
 // One head of K entries at column OFF of the lane's staged row; vb: its valid bits.  Returns the
 // action; adds the head's terms to logp / ent, or sets bad for a degenerate head.
 template <int OFF, int K, bool GREEDY>
@@ -223,22 +262,7 @@ __global__ void __launch_bounds__(kTile *kWaves) k_policy_sample(PolicyArgs a) {
       u[h] = (float)((x_new - 1u) >> 7) * (1.0f / 16777216.0f);
     }
   }
-  // the mask records: granule cc (of 6) of row `row`, 16 bits each
-#pragma unroll
-  for (int k = 0; k < (kTile * 6 + T - 1) / T; k++) {
-    const int q = k * T + tid, row = q / 6, cc = q % 6;
-    if (q < kTile * 6) {
-      uint32_t bits = 0;
-      if (row < rows) {
-        const size_t e = base + row;
-        const uint8_t *rec = a.mask_base + e * a.mask_stride;
-        if (a.agent) rec += (size_t)(a.agent[e] & 3u) * COG_OBS_PLAYER_STRIDE;
-        const uint4 v = reinterpret_cast<const uint4 *>(rec)[cc];
-        bits = nonzero_bytes(v.x) | nonzero_bytes(v.y) << 4 | nonzero_bytes(v.z) << 8 | nonzero_bytes(v.w) << 12;
-      }
-      reinterpret_cast<uint16_t *>(mbits)[q] = (uint16_t)bits;
-    }
-  }
+  stage_masks<T>(mbits, a.mask_base, a.mask_stride, a.agent, base, rows, tid);
   stage_logits<BF16, VEC, T>(tile, a.logits, a.ld, base, rows, tid);
   __syncthreads();
 
@@ -247,18 +271,13 @@ __global__ void __launch_bounds__(kTile *kWaves) k_policy_sample(PolicyArgs a) {
   uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0;
   if (live) {
     const float *row = tile + lane * kRowStride;
-    const uint64_t lo = (uint64_t)mbits[3 * lane] | (uint64_t)mbits[3 * lane + 1] << 32;       // bits 0..63
-    const uint64_t hi = (uint64_t)mbits[3 * lane + 1] | (uint64_t)mbits[3 * lane + 2] << 32;   // bits 32..95
-    if (wave == 0)
-      a0 = sample_head<COG_MASK_PLAY, 22, GREEDY>(row, (uint32_t)(lo >> COG_MASK_PLAY) & 0x3fffffu, u[0], logp, ent, bad);
-    if (wave == 1)
-      a1 = sample_head<COG_MASK_SPECIAL, 22, GREEDY>(row, (uint32_t)(lo >> COG_MASK_SPECIAL) & 0x3fffffu, u[1], logp, ent, bad);
-    if (wave == 2)
-      a2 = sample_head<COG_MASK_REMOVE, 22, GREEDY>(row, (uint32_t)(hi >> (COG_MASK_REMOVE - 32)) & 0x3fffffu, u[2], logp, ent,
-                                                    bad);
+    const HeadBits vb = head_bits(mbits, lane);
+    if (wave == 0) a0 = sample_head<COG_MASK_PLAY, 22, GREEDY>(row, vb.play, u[0], logp, ent, bad);
+    if (wave == 1) a1 = sample_head<COG_MASK_SPECIAL, 22, GREEDY>(row, vb.special, u[1], logp, ent, bad);
+    if (wave == 2) a2 = sample_head<COG_MASK_REMOVE, 22, GREEDY>(row, vb.remove, u[2], logp, ent, bad);
     if (wave == 3) {
-      a3 = sample_head<COG_MASK_MOVE, 7, GREEDY>(row, (uint32_t)(hi >> (COG_MASK_MOVE - 32)) & 0x7fu, u[3], logp, ent, bad);
-      a4 = sample_head<COG_MASK_SHOP, 19, GREEDY>(row, (uint32_t)(hi >> (COG_MASK_SHOP - 32)) & 0x7ffffu, u[4], logp, ent, bad);
+      a3 = sample_head<COG_MASK_MOVE, 7, GREEDY>(row, vb.move, u[3], logp, ent, bad);
+      a4 = sample_head<COG_MASK_SHOP, 19, GREEDY>(row, vb.shop, u[4], logp, ent, bad);
     }
   }
   if (wave > 0) {
@@ -298,7 +317,267 @@ void launch_form(const PolicyArgs &a, bool greedy, dim3 grid, hipStream_t st) {
     hipLaunchKernelGGL((k_policy_sample<BF16, VEC, false>), grid, dim3(kTile * kWaves), 0, st, a);
 }
 
+// ---- the policy evaluator (include/cog.h cog_policy_evaluate / cog_policy_evaluate_backward) ----
+// The same distribution seen from the learner's side: for recorded (mask, action) pairs and new
+// logits, the joint log-probability of the recorded actions and the entropy (forward), and the
+// gradient of both with respect to the logits (backward).  Both kernels keep the sampler's shape:
+// four waves per tile of 64 rows, the tile and the mask bits staged by the sampler's own code, the
+// heads split over the waves, lane r on row r.  The backward recomputes the head terms (the forward
+// saves nothing) and writes each head's gradient entries over the staged logits in place; after a
+// barrier the workgroup stores the tile, one contiguous block of the (n, 92) output, with 16-B
+// stores.  A row with a degenerate head or an illegal recorded action is flagged in LDS and stored
+// as zeros.  No atomics: the results are the same from run to run.
+
+struct EvalArgs {
+  size_t n;
+  const void *logits;
+  size_t ld;
+  const uint8_t *actions;
+  size_t action_stride;
+  const uint8_t *masks;
+  float *logp, *entropy;                                   // forward
+  const float *g_logp, *g_entropy;                         // backward
+  void *grad;
+};
+
+// The terms of one non-empty head of K entries at column OFF of the lane's staged row (vb: its valid
+// bits, a: the recorded action), in R = float or double: d_j = l_j - m (clamped finite, so that
+// 0 * d_j is 0), w_j = exp(d_j), Z = sum w, S = sum w_j d_j.  False for a degenerate head or an action
+// that is no valid entry.
+DEV float exp_r(float x) { return __expf(x); }
+DEV double exp_r(double x) { return exp(x); }
+
+template <int OFF, int K, typename R>
+DEV bool head_terms(const float *row, uint32_t vb, uint32_t a, R (&d)[K], R (&w)[K], float &m, R &Z, R &S) {
+  m = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    const float x = row[OFF + j];
+    const float l = ((vb >> j) & 1u) && x == x ? x : -INFINITY;
+    d[j] = l;
+    m = fmaxf(m, l);
+  }
+  if (!(fabsf(m) < INFINITY)) return false;                // +inf, or nothing above -inf
+  if (a >= (uint32_t)K || !((vb >> a) & 1u)) return false;
+  Z = 0;
+  S = 0;
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    d[j] = d[j] - (R)m;
+    d[j] = d[j] > (R)-3.0e38f ? d[j] : (R)-3.0e38f;
+    w[j] = exp_r(d[j]);
+    Z += w[j];
+    S += w[j] * d[j];
+  }
+  return true;
+}
+
+template <int OFF, int K>
+DEV void eval_head(const float *row, uint32_t vb, uint32_t a, float &logp, float &ent, bool &bad) {
+  if (vb == 0u) return;
+  float d[K], w[K], m, Z, S;
+  if (!head_terms<OFF, K, float>(row, vb, a, d, w, m, Z, S)) {
+    bad = true;
+    return;
+  }
+  const float x = row[OFF + a];                            // (a < K: checked)
+  const float logZ = logf(Z);
+  logp += (x == x ? x - m : -INFINITY) - logZ;
+  ent += logZ - S / Z;
+}
+
+// grad_j = g_lp (1[j = a] - p_j) - g_en p_j (log p_j + H), and log p_j + H = d_j - S / Z; zeros for
+// invalid entries and for an empty head.  R: the type the terms are computed in.  A float32 gradient
+// is computed in float.  A bfloat16 one is computed in double and narrowed to float here, so that the
+// value the store rounds to bfloat16 is the exact one's float32 neighbour: a float-computed value is
+// some 1e-7 off, and where the exact one lies that close to the midpoint of two bfloat16 values it
+// rounds to the wrong one of the two, a whole bfloat16 step away (a few entries in 10^5).
+template <int OFF, int K, typename R>
+DEV void grad_head(float *row, uint32_t vb, uint32_t a, float g_lp, float g_en, bool &bad) {
+  if (vb == 0u) {
+#pragma unroll
+    for (int j = 0; j < K; j++) row[OFF + j] = 0.0f;
+    return;
+  }
+  R d[K], w[K], Z, S;
+  float m;
+  if (!head_terms<OFF, K, R>(row, vb, a, d, w, m, Z, S)) {
+    bad = true;                                            // (the whole row is stored as zeros)
+    return;
+  }
+  const R rz = (R)1 / Z, c = S * rz;
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    const R p = w[j] * rz;
+    const R g = (R)g_lp * (((uint32_t)j == a ? (R)1 : (R)0) - p) - (R)g_en * (p * (d[j] - c));
+    row[OFF + j] = (vb >> j) & 1u ? (float)g : 0.0f;
+  }
+}
+
+DEV uint32_t bf16_round(float f) {                         // round to nearest even; NaN stays NaN
+  const uint32_t u = __float_as_uint(f);
+  return f != f ? 0x7fc0u : (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+
+template <bool BF16, bool VEC>
+__global__ void __launch_bounds__(kTile *kWaves) k_policy_eval(EvalArgs a) {
+  __shared__ float tile[kTile * kRowStride];
+  __shared__ uint32_t mbits[kTile * 3];
+  __shared__ float part[(kWaves - 1) * 3 * kTile];         // waves 1..3: logp, entropy, bad
+  constexpr int T = kTile * kWaves;
+  const int tid = (int)threadIdx.x, lane = tid & (kTile - 1), wave = tid / kTile;
+  const size_t base = (size_t)blockIdx.x * kTile;
+  const int rows = a.n - base < (size_t)kTile ? (int)(a.n - base) : kTile;
+  const size_t i = base + lane;
+  const bool live = lane < rows;
+  uint32_t act = 0, act4 = 0;                              // the wave's action byte (wave 3: bytes 3 and 4)
+  if (live) {
+    const uint8_t *rec = a.actions + i * a.action_stride;
+    act = rec[wave];
+    if (wave == 3) act4 = rec[4];
+  }
+  stage_masks<T>(mbits, a.masks, COG_MASK_BYTES, nullptr, base, rows, tid);
+  stage_logits<BF16, VEC, T>(tile, a.logits, a.ld, base, rows, tid);
+  __syncthreads();
+
+  float logp = 0.0f, ent = 0.0f;
+  bool bad = false;
+  if (live) {
+    const float *row = tile + lane * kRowStride;
+    const HeadBits vb = head_bits(mbits, lane);
+    if (wave == 0) eval_head<COG_MASK_PLAY, 22>(row, vb.play, act, logp, ent, bad);
+    if (wave == 1) eval_head<COG_MASK_SPECIAL, 22>(row, vb.special, act, logp, ent, bad);
+    if (wave == 2) eval_head<COG_MASK_REMOVE, 22>(row, vb.remove, act, logp, ent, bad);
+    if (wave == 3) {
+      eval_head<COG_MASK_MOVE, 7>(row, vb.move, act, logp, ent, bad);
+      eval_head<COG_MASK_SHOP, 19>(row, vb.shop, act4, logp, ent, bad);
+    }
+  }
+  if (wave > 0) {
+    float *p = part + (wave - 1) * 3 * kTile + lane;
+    p[0] = logp;
+    p[kTile] = ent;
+    p[2 * kTile] = bad ? 1.0f : 0.0f;
+  }
+  __syncthreads();
+  if (wave > 0 || !live) return;
+#pragma unroll
+  for (int w = 1; w < kWaves; w++) {
+    const float *p = part + (w - 1) * 3 * kTile + lane;
+    logp += p[0];
+    ent += p[kTile];
+    bad = bad || p[2 * kTile] != 0.0f;
+  }
+  if (a.logp) a.logp[i] = bad ? __uint_as_float(0x7fc00000u) : logp;
+  if (a.entropy) a.entropy[i] = bad ? __uint_as_float(0x7fc00000u) : ent;
+}
+
+template <bool BF16, bool VEC>
+__global__ void __launch_bounds__(kTile *kWaves) k_policy_eval_backward(EvalArgs a) {
+  __shared__ float tile[kTile * kRowStride];
+  __shared__ uint32_t mbits[kTile * 3];
+  __shared__ uint32_t badrow[kWaves * kTile];              // per wave and row: its head is degenerate / the action illegal
+  constexpr int T = kTile * kWaves;
+  const int tid = (int)threadIdx.x, lane = tid & (kTile - 1), wave = tid / kTile;
+  const size_t base = (size_t)blockIdx.x * kTile;
+  const int rows = a.n - base < (size_t)kTile ? (int)(a.n - base) : kTile;
+  const size_t i = base + lane;
+  const bool live = lane < rows;
+  uint32_t act = 0, act4 = 0;
+  float g_lp = 0.0f, g_en = 0.0f;
+  if (live) {
+    const uint8_t *rec = a.actions + i * a.action_stride;
+    act = rec[wave];
+    if (wave == 3) act4 = rec[4];
+    if (a.g_logp) g_lp = a.g_logp[i];
+    if (a.g_entropy) g_en = a.g_entropy[i];
+  }
+  stage_masks<T>(mbits, a.masks, COG_MASK_BYTES, nullptr, base, rows, tid);
+  stage_logits<BF16, VEC, T>(tile, a.logits, a.ld, base, rows, tid);
+  __syncthreads();
+
+  using R = typename std::conditional<BF16, double, float>::type;   // (see grad_head)
+  bool bad = false;
+  if (live) {
+    float *row = tile + lane * kRowStride;
+    const HeadBits vb = head_bits(mbits, lane);
+    if (wave == 0) grad_head<COG_MASK_PLAY, 22, R>(row, vb.play, act, g_lp, g_en, bad);
+    if (wave == 1) grad_head<COG_MASK_SPECIAL, 22, R>(row, vb.special, act, g_lp, g_en, bad);
+    if (wave == 2) grad_head<COG_MASK_REMOVE, 22, R>(row, vb.remove, act, g_lp, g_en, bad);
+    if (wave == 3) {
+      grad_head<COG_MASK_MOVE, 7, R>(row, vb.move, act, g_lp, g_en, bad);
+      grad_head<COG_MASK_SHOP, 19, R>(row, vb.shop, act4, g_lp, g_en, bad);
+    }
+  }
+  badrow[tid] = bad ? 1u : 0u;
+  __syncthreads();
+
+  // the tile is rows x 23 quads of the contiguous output; quad q is columns 4 (q % 23).. of row q / 23
+  const int total = rows * kQuads;
+  auto quad = [&](int q, float (&v)[4]) {
+    const int row = q / kQuads;
+    const bool zero = (badrow[row] | badrow[kTile + row] | badrow[2 * kTile + row] | badrow[3 * kTile + row]) != 0u;
+    const float *p = tile + row * kRowStride + 4 * (q % kQuads);
+#pragma unroll
+    for (int k = 0; k < 4; k++) v[k] = zero ? 0.0f : p[k];
+  };
+  if (!BF16) {
+    float *out = static_cast<float *>(a.grad) + base * kCols;
+#pragma unroll
+    for (int k = 0; k < (kTile * kQuads + T - 1) / T; k++) {
+      const int q = k * T + tid;
+      if (q < total) {
+        float v[4];
+        quad(q, v);
+        *reinterpret_cast<float4 *>(out + 4 * (size_t)q) = make_float4(v[0], v[1], v[2], v[3]);
+      }
+    }
+  } else {
+    // a 16-B granule holds two quads of 8 B; the block's last granule may be half of one
+    uint16_t *out = static_cast<uint16_t *>(a.grad) + base * kCols;
+#pragma unroll
+    for (int k = 0; k < (kTile * kQuads / 2 + T - 1) / T; k++) {
+      const int p = k * T + tid, g = 2 * p;
+      if (g < total) {
+        float v[4];
+        quad(g, v);
+        const uint2 lo = make_uint2(bf16_round(v[0]) | bf16_round(v[1]) << 16, bf16_round(v[2]) | bf16_round(v[3]) << 16);
+        if (g + 1 < total) {
+          quad(g + 1, v);
+          *reinterpret_cast<uint4 *>(out + 8 * (size_t)p) =
+              make_uint4(lo.x, lo.y, bf16_round(v[0]) | bf16_round(v[1]) << 16, bf16_round(v[2]) | bf16_round(v[3]) << 16);
+        } else {
+          *reinterpret_cast<uint2 *>(out + 8 * (size_t)p) = lo;
+        }
+      }
+    }
+  }
+}
+
 }  // namespace
+
+int launch_policy_eval(const PolicyEval &p, bool backward, void *stream) {
+  if (!p.n) return 0;
+  const EvalArgs a{p.n, p.logits, p.ld, p.actions, p.action_stride, p.masks, p.logp, p.entropy, p.g_logp, p.g_entropy, p.grad};
+  const dim3 grid((unsigned)((p.n + kTile - 1) / kTile)), block(kTile * kWaves);
+  hipStream_t st = (hipStream_t)stream;
+  const bool aligned = (reinterpret_cast<uintptr_t>(p.logits) & 15u) == 0;
+  const bool vec = aligned && (p.bf16 ? p.ld == (size_t)kCols || p.ld % 8 == 0 : p.ld % 4 == 0);   // (as the sampler)
+#define COG_EVAL_LAUNCH(B, V)                                                                   \
+  do {                                                                                          \
+    if (backward)                                                                               \
+      hipLaunchKernelGGL((k_policy_eval_backward<B, V>), grid, block, 0, st, a);                \
+    else                                                                                        \
+      hipLaunchKernelGGL((k_policy_eval<B, V>), grid, block, 0, st, a);                         \
+  } while (0)
+  if (p.bf16) {
+    if (vec) COG_EVAL_LAUNCH(true, true); else COG_EVAL_LAUNCH(true, false);
+  } else {
+    if (vec) COG_EVAL_LAUNCH(false, true); else COG_EVAL_LAUNCH(false, false);
+  }
+#undef COG_EVAL_LAUNCH
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 
 int launch_policy_sample(const PolicyLaunch &p, void *stream) {
   if (!p.n) return 0;

@@ -361,6 +361,35 @@ PYBIND11_MODULE(_city_of_gold, m) {
       "device"_a = 0, "bytes"_a = (size_t)1 << 31, "iters"_a = 5,
       "read + write GB/s of the engine's device copy kernel (measurement)");
   m.def(
+      "policy_evaluate_raw",
+      [](size_t n, uintptr_t d_logits, int dtype, size_t ld, uintptr_t d_actions, size_t action_stride, uintptr_t d_masks,
+         uintptr_t d_logp, uintptr_t d_entropy, uintptr_t d_grad_logp, uintptr_t d_grad_entropy, uintptr_t d_grad_logits,
+         int device, int64_t stream, bool backward) {
+        // cog_policy_evaluate / cog_policy_evaluate_backward over raw device pointers (city_of_gold
+        // policy_evaluate is the torch face): dtype 0 float32 / 1 bfloat16, stream a hipStream_t
+        // handle (0 = the null stream; -1: none, which is refused)
+        cog_policy_eval_args a{};
+        a.n = n;
+        a.d_logits = reinterpret_cast<const void *>(d_logits);
+        a.logits_dtype = dtype;
+        a.ld = ld;
+        a.d_actions = reinterpret_cast<const uint8_t *>(d_actions);
+        a.action_stride = action_stride;
+        a.d_masks = reinterpret_cast<const void *>(d_masks);
+        a.d_logp = reinterpret_cast<float *>(d_logp);
+        a.d_entropy = reinterpret_cast<float *>(d_entropy);
+        a.d_grad_logp = reinterpret_cast<const float *>(d_grad_logp);
+        a.d_grad_entropy = reinterpret_cast<const float *>(d_grad_entropy);
+        a.d_grad_logits = reinterpret_cast<void *>(d_grad_logits);
+        a.device = device;
+        a.stream = stream < 0 ? COG_NO_STREAM : reinterpret_cast<void *>((uintptr_t)stream);
+        check(backward ? cog_policy_evaluate_backward(&a) : cog_policy_evaluate(&a));
+      },
+      "n"_a, "d_logits"_a, "dtype"_a, "ld"_a, "d_actions"_a, "action_stride"_a, "d_masks"_a, "d_logp"_a = 0,
+      "d_entropy"_a = 0, "d_grad_logp"_a = 0, "d_grad_entropy"_a = 0, "d_grad_logits"_a = 0, "device"_a = 0,
+      "stream"_a = 0, "backward"_a = false,
+      "log-probability and entropy of recorded actions under new logits, or (backward=True) their gradient");
+  m.def(
       "time_stream_mix",
       [](int device, size_t bytes, int iters) {
         double gbs = 0.0;

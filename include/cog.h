@@ -229,6 +229,43 @@ typedef struct cog_policy_args {
   uint32_t flags; void *stream;         /* caller's hipStream_t, or COG_NO_STREAM */
 } cog_policy_args;
 COG_API int cog_sampler_sample_policy(cog_sampler *s, const cog_policy_args *a);
+/* Policy evaluator (an addition): the distribution cog_sampler_sample_policy draws from, seen from
+ * the learner's side.  For n rows of new logits (92 per row in ActionMask byte order, float32 or
+ * bfloat16 widened exactly, rows `ld` elements apart, ld >= 92) and the recorded pair of each row
+ * -- its 128-byte ActionMask record (a byte != 0 is valid) and its action record, whose bytes 0..4
+ * are play, play_special, remove, move, get_from_shop, records `action_stride` bytes apart -- the
+ * forward gives the joint log-probability of the recorded actions and the entropy, the backward
+ * their gradient with respect to the logits.  n is any size; no env or sampler handle is involved.
+ * Forward, per head h (offset, size) = (0,22), (22,22), (44,22), (66,7), (73,19) with at least one
+ * valid entry, over the valid entries in float32 (a NaN logit counts as -inf): m = max l,
+ * d_j = l_j - m, w_j = exp(d_j), Z = sum w, p_j = w_j / Z, H = log Z - sum w_j d_j / Z; with a the
+ * recorded action of the head, logp += d_a - log Z and entropy += H.  A head with no valid entry
+ * contributes nothing and its action byte is ignored.
+ * A row is bad when, for some non-empty head, the valid entries hold +inf or nothing but -inf / NaN
+ * (the sampler's degenerate case), or the recorded action is no valid entry (a >= size, or its mask
+ * byte is 0): its logp and entropy are NaN and its gradient row is all zeros whatever comes in.
+ * Backward, with the incoming gradients g_lp[i], g_en[i] (float32; a NULL pointer counts as zeros):
+ * for a valid entry j of a non-empty head of a good row
+ *   grad_j = g_lp (1[j = a] - p_j) - g_en p_j (log p_j + H),   the g_en term 0 where p_j = 0,
+ * and every other column (invalid entries, empty heads) is 0.  It recomputes the head terms from
+ * the logits, masks and actions: the forward saves nothing.  d_grad_logits: n contiguous rows of
+ * 92 in the logits' dtype (bfloat16: the head terms are computed in double, narrowed to float32 and
+ * rounded to nearest even: float32 terms would round a few entries in 10^5 the other way, a whole
+ * bfloat16 step off).  No atomics: the same inputs give the
+ * same bits.  Each call is one kernel on `stream` of `device`; neither waits on the host, and
+ * COG_NO_STREAM is refused (there is no stream of the library's own).  n == 0 launches nothing. */
+typedef struct cog_policy_eval_args {
+  size_t n;
+  const void *d_logits; int logits_dtype; size_t ld;       /* COG_LOGITS_*, ld >= 92 elements        */
+  const uint8_t *d_actions; size_t action_stride;          /* bytes between records, >= 5            */
+  const void *d_masks;                                     /* n ActionMask records, 16-byte aligned  */
+  float *d_logp; float *d_entropy;                         /* forward outputs; may be NULL           */
+  const float *d_grad_logp; const float *d_grad_entropy;   /* backward inputs; NULL = zeros          */
+  void *d_grad_logits;                                     /* backward output: n rows of 92, logits' dtype, 16-byte aligned */
+  int device; void *stream;                                /* device ordinal; caller's hipStream_t (NULL: the null stream) */
+} cog_policy_eval_args;
+COG_API int cog_policy_evaluate(const cog_policy_eval_args *a);            /* forward  */
+COG_API int cog_policy_evaluate_backward(const cog_policy_eval_args *a);   /* backward */
 COG_API cog_action_t *cog_sampler_actions(cog_sampler *s);   /* persistent host view */
 COG_API void *cog_sampler_device_actions(cog_sampler *s);    /* device view (shard 0) */
 COG_API void *cog_sampler_shard_device_actions(cog_sampler *s, int shard);
