@@ -244,6 +244,8 @@ COG_API int cog_sampler_sample_policy(cog_sampler *s, const cog_policy_args *a);
  * A row is bad when, for some non-empty head, the valid entries hold +inf or nothing but -inf / NaN
  * (the sampler's degenerate case), or the recorded action is no valid entry (a >= size, or its mask
  * byte is 0): its logp and entropy are NaN and its gradient row is all zeros whatever comes in.
+ * A recorded action on a valid entry that holds -inf (or NaN) beside finite valid ones is no bad
+ * row: p_a = 0, so logp is -inf, the entropy is that of the other entries and grad_a = g_lp.
  * Backward, with the incoming gradients g_lp[i], g_en[i] (float32; a NULL pointer counts as zeros):
  * for a valid entry j of a non-empty head of a good row
  *   grad_j = g_lp (1[j = a] - p_j) - g_en p_j (log p_j + H),   the g_en term 0 where p_j = 0,

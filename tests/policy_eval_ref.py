@@ -15,7 +15,8 @@ def evaluate(logits, actions, masks, g_lp=None, g_en=None, dtype=np.float64):
     recorded action of each head; masks: (n, >= 92), non-zero = valid; g_lp, g_en: (n,) incoming
     gradients (None = zeros).
     Returns dict(logp, entropy (n,) dtype: NaN for a bad row; grad (n, 92) dtype: zeros for a bad row;
-    bad (n,) bool; nonempty (n, 5) bool)."""
+    bad (n,) bool; nonempty (n, 5) bool).  A recorded action on a valid -inf entry beside finite valid
+    ones is no bad row: logp is -inf and the gradient entry at the action is g_lp."""
     logits = np.asarray(logits)
     actions = np.asarray(actions)
     n = logits.shape[0]

@@ -26,9 +26,10 @@ def mr_next(x):
     return x * np.uint64(16807) % np.uint64(MINSTD_M)
 
 
-def sample(logits, masks, states=None, greedy=False, dtype=np.float64):
+def sample(logits, masks, states=None, greedy=False, dtype=np.float64, strict=True):
     """logits: (n, 92) float array (the float32 / widened bfloat16 values); masks: (n, >= 92), non-zero
-    = valid; states: (n,) uint64 sampler states (None with greedy).
+    = valid; states: (n,) uint64 sampler states (None with greedy).  strict=False is the wrong rule
+    C_j >= u Z, kept so that a test can show that its cases tell the two apart.
     Returns dict(actions (n, 5) int, logp, entropy (n,) dtype, near (n, 5) bool: some valid prefix sum
     lies within the band of u Z, states: the states after the call)."""
     logits = np.asarray(logits)
@@ -65,7 +66,7 @@ def sample(logits, masks, states=None, greedy=False, dtype=np.float64):
                 x = mr_next(x)
                 u = (((x - np.uint64(1)) >> np.uint64(7)).astype(np.float64) * 2.0 ** -24).astype(dtype)
                 t = (u * Z).astype(dtype)
-                over = (C > t[:, None]) & valid
+                over = ((C > t[:, None]) if strict else (C >= t[:, None])) & valid
                 last = k - 1 - valid[:, ::-1].argmax(1)
                 a = np.where(over.any(1), over.argmax(1), last)
                 a = np.where(degen, best, a)
