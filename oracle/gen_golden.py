@@ -14,7 +14,9 @@ observations, selected_action_masks, rewards, dones, agent_selection, infos, act
 (SURVEY App. B.3), for ONE env.  Batch runs are compared env by env (envs are independent:
 env i of a batch == a 1-env batch seeded seed+i, sampler seeded sseed+i).
 
-    python oracle/gen_golden.py            # writes tests/golden/*.npz and *.json
+    python oracle/gen_golden.py              # writes tests/golden/*.npz and *.json
+    python oracle/gen_golden.py --workloads  # ref_workloads.{npz,json} only
+    python oracle/gen_golden.py --lategame   # ref_lategame.json + ref_lategame_digests.npz only
 """
 from __future__ import annotations
 
@@ -204,11 +206,94 @@ def workloads():
                        workloads=meta), f, indent=0)
 
 
+# The late game, pinned by the reference: 1-env batches, stored masks, one map piece and max_steps
+# 100,000, so that episodes end when a player reaches the end hex and the uniform sampler plays
+# every special (cards 15..20) and the remove path.  HARD with 4 players is the only family the
+# reference built against libstdc++ 11 can run for long with auto-resets (EASY and MEDIUM erase
+# past the end of valid_indices, fewer players abort on a B start).
+LATEGAME = dict(name="lategame_hard_4p_1piece", n_players=4, n_pieces=1, difficulty=2, max_steps=100000,
+                mode="sto", steps=6000, first_seed=6000, screened=256, keep=8, min_each_special=20)
+
+
+def lategame_screen(seed, cfg):
+    """Oracle-only run of one seed: None if the reference cannot run it (a REF_UNSAFE flag anywhere
+    in the horizon, or a failed map generation), else its counts (natural ends, specials per card,
+    removes).  The effective action follows the step's precedence:
+    play > play_special > move > get_from_shop > remove."""
+    o, s = po.OracleVec(1), po.OracleSampler(1, seed)
+    try:
+        o.reset(seed, cfg["n_players"], cfg["n_pieces"], cfg["difficulty"], cfg["max_steps"])
+    except RuntimeError:
+        return None
+    ends, removes, specials = [], 0, {c: 0 for c in range(15, 21)}
+    for t in range(cfg["steps"]):
+        if o.flags(0) & po.REF_UNSAFE:
+            return None
+        s.sample(po.stored_masks(o))
+        a = s.actions[0]
+        try:
+            o.step(s.actions)
+        except RuntimeError:
+            return None
+        if not a["play"]:
+            if a["play_special"]:
+                specials[int(a["play_special"]) - 1] += 1
+            elif not a["move"] and not a["get_from_shop"] and a["remove"]:
+                removes += 1
+        if o.dones[0] and (o.rewards[0] > 0).any():
+            ends.append(t)
+    if o.flags(0) & po.REF_UNSAFE:
+        return None
+    return dict(natural_ends=ends, specials=specials, removes=removes)
+
+
+def lategame():
+    cfg = LATEGAME
+    # more than half of the envs never buy a special card under the uniform sampler: of the
+    # screened seeds with a natural end, keep those that play the most kinds of specials (then the
+    # most specials), in seed order
+    cands = []
+    for seed in range(cfg["first_seed"], cfg["first_seed"] + cfg["screened"]):
+        c = lategame_screen(seed, cfg)
+        if c is not None and c["natural_ends"]:
+            cands.append((seed, c))
+    print(f"lategame: {len(cands)} of {cfg['screened']} screened seeds are reference-safe with a natural end")
+    cands.sort(key=lambda sc: (-sum(v > 0 for v in sc[1]["specials"].values()), -sum(sc[1]["specials"].values())))
+    kept, arrays = [], {}
+    for seed, c in sorted(cands[:cfg["keep"]], key=lambda sc: sc[0]):
+        dig, resets = ref_trace(seed, cfg["n_players"], cfg["n_pieces"], cfg["difficulty"], cfg["max_steps"],
+                                seed, cfg["mode"], cfg["steps"])
+        assert resets == len(c["natural_ends"])
+        arrays[f"{cfg['name']}__{len(kept)}"] = np.frombuffer(b"".join(dig), dtype=np.uint8).reshape(-1, 8)
+        kept.append(dict(seed=seed, sampler_seed=seed, steps=cfg["steps"], natural_ends=c["natural_ends"],
+                         specials={str(k): v for k, v in c["specials"].items()}, removes=c["removes"]))
+        print(f"lategame: seed {seed}: ends at {c['natural_ends']}, specials {list(c['specials'].values())}, "
+              f"{c['removes']} removes")
+    assert len(kept) == cfg["keep"], f"only {len(kept)} seeds with a natural end among {cfg['screened']}"
+    totals = {str(c): sum(e["specials"][str(c)] for e in kept) for c in range(15, 21)}
+    assert min(totals.values()) >= cfg["min_each_special"], totals
+    np.savez_compressed(os.path.join(OUT, "ref_lategame_digests.npz"), **arrays)
+    with open(os.path.join(OUT, "ref_lategame.json"), "w") as f:
+        json.dump(dict(source="oracle/_ref (unmodified reference core) via oracle/gen_golden.py --lategame",
+                       digest="sha256[:8] over named leaves of obs, sel, rewards, dones, agent_sel, infos, actions",
+                       digests_file="ref_lategame_digests.npz (key <name>__<k>, uint8[steps+1, 8]: after reset, "
+                                    "then after every step)",
+                       name=cfg["name"], n_players=cfg["n_players"], n_pieces=cfg["n_pieces"],
+                       difficulty=cfg["difficulty"], max_steps=cfg["max_steps"], mode=cfg["mode"],
+                       steps=cfg["steps"], total_specials=totals,
+                       total_natural_ends=sum(len(e["natural_ends"]) for e in kept),
+                       total_removes=sum(e["removes"] for e in kept), envs=kept), f, indent=0)
+    print(f"lategame: {len(kept)} seeds, specials {totals}")
+
+
 def main():
     assert po.ref_available(), "build the reference first: make -C oracle ref"
     os.makedirs(OUT, exist_ok=True)
     if "--workloads" in sys.argv:
         workloads()
+        return
+    if "--lategame" in sys.argv:
+        lategame()
         return
     t = traces()
     arrays = {}
