@@ -11,6 +11,7 @@ Outputs (git-ignored, shipped to the GPU box by the snapshot):
 """
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 import sys
@@ -33,8 +34,6 @@ LIB_FENCE = os.path.join(OUT, "libcog_hip_fence.so")
 EXT = os.path.join(OUT, "_city_of_gold" + sysconfig.get_config_var("EXT_SUFFIX"))
 
 ENGINE_SRCS = [os.path.join(CSRC, f) for f in ("cog_engine.hip", "cog_abi.cpp", "cog_policy.hip")]
-ENGINE_DEPS = ENGINE_SRCS + [os.path.join(CSRC, f) for f in ("cog_engine.h", "cog_policy.h", "cog_tables.h", "cog_rng.h")] + [
-    os.path.join(INCLUDE, f) for f in ("cog.h", "cog_types.h")]
 EXT_SRCS = [os.path.join(CSRC, "pybind_module.cpp")]
 
 
@@ -51,13 +50,13 @@ def _run(cmd, cwd=None):
 
 
 OBJ = os.path.join(PKG, "build")
-HEADERS = [os.path.join(CSRC, f) for f in ("cog_engine.h", "cog_policy.h", "cog_tables.h", "cog_rng.h")] + [
-    os.path.join(INCLUDE, f) for f in ("cog.h", "cog_types.h")]
+# every header a source may include: csrc's own (at any depth) and the public ones
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "**", "*.h"), recursive=True) + glob.glob(os.path.join(INCLUDE, "*.h")))
 
 
 def _compile_cmd(src, obj, defs=()):
     # max-ilp scheduling: the rollout runs one wave per SIMD, so only instruction-level
-    # parallelism hides latency (1 % faster than the default, tools/flags_exp.sh); loop heads on
+    # parallelism hides latency (1 % faster than the default, round 2's flags A/B); loop heads on
     # 64-B instruction-cache lines: the trio's step time otherwise moves by 1-2 % with unrelated
     # code size changes (profiles/r06_compact_decks_ab.txt)
     return [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-c",

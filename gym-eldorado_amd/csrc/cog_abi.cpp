@@ -1640,9 +1640,6 @@ static int runner_launch_fused(cog_runner *r, int steps) {
                               k.lean_clock + (uint64_t)kk < (uint64_t)r->env->max_steps;
         cog::DevState sc = s;
         sc.cdeck_ok = trio && k.cdeck_ok ? 1u : 0u;
-#ifdef COG_NO_CDECK                                        // (A/B probe builds: the DeckObs loads always)
-        sc.cdeck_ok = 0u;
-#endif
         if (cog::launch_rollout(sc, src, kk, q.d_rng, q.d_actions, k.stream, r->env->n_players >= 3, &k.park_seq,
                                 no_fixup))
           return fail(COG_ERR_HIP, std::string("rollout launch failed: ") + hipGetErrorString(hipGetLastError()));

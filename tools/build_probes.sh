@@ -5,8 +5,13 @@
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p tools/bin
-F="-O3 -std=c++17 -ffp-contract=off -mllvm -amdgpu-sched-strategy=max-ilp -falign-loops=64 -Iinclude -Igym-eldorado_amd/csrc"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 $F tools/duoprobe.cpp -o tools/bin/duoprobe 2>/dev/null &
-/opt/rocm/bin/hipcc --offload-arch=gfx950 $F -DCOG_STAMPS tools/duoprobe.cpp -o tools/bin/duoprobe_st 2>/dev/null &
-wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 tools/chainprobe.hip -o tools/bin/chainprobe 2>/dev/null
+F="-w -O3 -std=c++17 -ffp-contract=off -mllvm -amdgpu-sched-strategy=max-ilp -falign-loops=64 -Iinclude -Igym-eldorado_amd/csrc"
+# (cog_policy.hip: the ABI that duoprobe.cpp includes links the policy kernels' launchers)
+P=gym-eldorado_amd/csrc/cog_policy.hip
+/opt/rocm/bin/hipcc --offload-arch=gfx950 $F tools/duoprobe.cpp $P -o tools/bin/duoprobe &
+a=$!
+/opt/rocm/bin/hipcc --offload-arch=gfx950 $F -DCOG_STAMPS tools/duoprobe.cpp $P -o tools/bin/duoprobe_st &
+b=$!
+wait $a
+wait $b
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -w -O3 tools/chainprobe.hip -o tools/bin/chainprobe

@@ -31,8 +31,10 @@ ENCODE = "void cog::k_encode_lds<true>"
 
 def engine_hash():
     h = hashlib.sha256()
-    for f in ("cog_engine.hip", "cog_engine.h", "cog_tables.h", "cog_rng.h"):
-        with open(os.path.join(ROOT, "gym-eldorado_amd", "csrc", f), "rb") as fh:
+    csrc = os.path.join(ROOT, "gym-eldorado_amd", "csrc")
+    parts = sorted("engine/" + f for f in os.listdir(os.path.join(csrc, "engine")) if f.endswith(".h"))
+    for f in ["cog_engine.hip", *parts, "cog_engine.h", "cog_tables.h", "cog_rng.h"]:
+        with open(os.path.join(csrc, f), "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]
 
