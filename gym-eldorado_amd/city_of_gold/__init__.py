@@ -20,6 +20,8 @@ entropy from a policy's logits on the GPU, feeding envs.step_device with no host
 For the update, policy_evaluate(logits, actions, masks) gives the log-probability of recorded
 actions and the entropy under new logits, with gradients (a torch.autograd.Function over two HIP
 kernels), and mask_records(envs, source) copies the masks a trainer has to record with them.
+turn_gae(values, agents, rewards, dones, last_values) turns a recorded window into per-seat
+advantages and returns (GAE over each seat's own rows of each episode), one HIP kernel.
 
 All computation runs in libcog_hip.so on a gfx950 GPU.  There is no CPU fallback: creating an
 environment without a usable device raises RuntimeError.
@@ -354,6 +356,79 @@ def policy_evaluate(logits, actions, masks):
     return _policy_evaluate_function().apply(logits, actions, masks)
 
 
+def turn_gae(values, agents, rewards, dones, last_values=None, *, gamma=0.99, lam=0.95):
+    """Per-seat generalised advantage estimation over a time-major window of a turn-based rollout:
+    one HIP kernel on torch's current stream, no atomics (the same inputs give the same bits),
+    nothing waits on the host.  Returns (advantages, returns), two new contiguous float32 (T, n)
+    tensors; there are no gradients (advantages are targets).
+
+    Row t of env i holds the step of seat a = agents[t, i] & 3 (agent_selection BEFORE the step) and
+    v = values[t, i], that seat's value estimate there; dones[t, i] and rewards[t, i, :] are the
+    env's views AFTER the step.  rewards are read only where dones is set (the engine's rewards view
+    is stale between dones: elsewhere it may hold anything, NaN included).  A done of any kind ends
+    the episode, and the next row belongs to a new one.  Walking t from T - 1 down to 0 with, per
+    seat p, nv[p] = last_values[i, p] (0 when None), A[p] = 0, R[p] = 0:
+      1. if dones[t, i]: for all four seats nv[p] = 0, A[p] = 0, R[p] = rewards[t, i, p];
+      2. for a only: delta = R[a] + gamma nv[a] - v; A[a] = delta + gamma lam A[a];
+         advantages[t, i] = A[a]; returns[t, i] = A[a] + v; nv[a] = v; R[a] = 0.
+    gamma discounts per own decision of a seat, not per env row; the terminal reward lands
+    undiscounted on each seat's last row of its episode.  last_values[i, p] is seat p's value at the
+    state after the last row (a record holds all four players, so a net can give it for any seat).
+
+    values: (T, n) float32 on a GPU, stride(1) == 1, stride(0) >= n (a [:, :n] view of a wider buffer
+    is taken as is); agents: (T, n) uint8 and dones: (T, n) uint8 or bool, the same stride rule;
+    rewards: (T, n, 4) float32, strides (>= 4 n, 4, 1) with 16-byte aligned rows; last_values:
+    contiguous (n, 4) float32 or None; all on one device.  T == 0 or n == 0 launches nothing."""
+    import torch
+    who = "turn_gae"
+    named = [("values", values), ("agents", agents), ("rewards", rewards), ("dones", dones)]
+    if last_values is not None:
+        named.append(("last_values", last_values))
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{who}: {name} must be a torch tensor")
+    if values.device.type != "cuda":
+        raise ValueError(f"{who}: values are on device {values.device}, not on a GPU")
+    if values.dim() != 2:
+        raise ValueError(f"{who}: values have shape {tuple(values.shape)}, expected (T, n)")
+    T, n = values.shape
+    for name, t in named[1:]:
+        if t.device != values.device:
+            raise ValueError(f"{who}: {name} are on device {t.device}, the values on {values.device}")
+    want = {"values": (torch.float32,), "agents": (torch.uint8,), "rewards": (torch.float32,),
+            "dones": (torch.uint8, torch.bool), "last_values": (torch.float32,)}
+    for name, t in named:
+        if t.dtype not in want[name]:
+            raise ValueError(f"{who}: {name} dtype {t.dtype} is not " + " or ".join(str(d) for d in want[name]))
+    shapes = {"agents": (T, n), "rewards": (T, n, 4), "dones": (T, n), "last_values": (n, 4)}
+    for name, t in named[1:]:
+        if tuple(t.shape) != shapes[name]:
+            raise ValueError(f"{who}: {name} have shape {tuple(t.shape)}, expected {shapes[name]}")
+    out = (torch.empty((T, n), dtype=torch.float32, device=values.device),
+           torch.empty((T, n), dtype=torch.float32, device=values.device))
+    if T == 0 or n == 0:
+        return out
+    for name, t in named[:4]:
+        inner = 4 if name == "rewards" else 1              # elements per env
+        if t.dim() == 3 and t.stride(2) != 1:
+            raise ValueError(f"{who}: {name} strides {tuple(t.stride())}: the inner stride must be 1")
+        if (n > 1 and t.stride(1) != inner) or (T > 1 and t.stride(0) < inner * n):
+            raise ValueError(f"{who}: {name} strides {tuple(t.stride())}: the env stride must be {inner} and the row "
+                             f"stride at least {inner * n}")
+    rewards_ld = rewards.stride(0) if T > 1 else 4 * n
+    if rewards_ld % 4 or rewards.data_ptr() % 16:
+        raise ValueError(f"{who}: rewards strides {tuple(rewards.stride())}, storage offset {rewards.storage_offset()}: "
+                         "the rows must be 16-byte aligned")
+    if last_values is not None and not last_values.is_contiguous():
+        raise ValueError(f"{who}: last_values strides {tuple(last_values.stride())}: it must be contiguous")
+    ld = lambda t: t.stride(0) if T > 1 else n             # noqa: E731
+    dev = values.device.index
+    _C.policy_gae_raw(T, n, values.data_ptr(), ld(values), agents.data_ptr(), ld(agents), rewards.data_ptr(), rewards_ld,
+                      dones.data_ptr(), ld(dones), 0 if last_values is None else last_values.data_ptr(), float(gamma),
+                      float(lam), out[0].data_ptr(), out[1].data_ptr(), dev, int(torch.cuda.current_stream(dev).cuda_stream))
+    return out
+
+
 from .single import cog_env  # noqa: E402  (src/pybind/single_env.cpp: the single-env API)
 
 get_vec_env = _getter(vec.sampler, VEC_ENV_CLS, _make_env_cls)
@@ -369,4 +444,4 @@ del _n, _m
 __all__ = ["vec", "Difficulty", "EASY", "MEDIUM", "HARD", "ObsData", "ActionMask", "ActionData", "Info",
            "DeckObs", "SharedObservation", "PlayerData", "PlayerObservation", "action_sampler", "get_vec_env",
            "get_vec_sampler", "get_runner", "device_count", "device_tensors", "stream_handle", "cog_env", "policy_evaluate",
-           "mask_records"]
+           "mask_records", "turn_gae"]

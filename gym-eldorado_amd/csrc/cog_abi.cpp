@@ -1453,6 +1453,56 @@ static int policy_evaluate(const cog_policy_eval_args *a, bool backward) {
 int cog_policy_evaluate(const cog_policy_eval_args *a) { return policy_evaluate(a, false); }
 int cog_policy_evaluate_backward(const cog_policy_eval_args *a) { return policy_evaluate(a, true); }
 
+// Per-seat advantage estimation (cog_policy.hip k_turn_gae): as the evaluator, one kernel on the
+// caller's stream on the caller's device.
+int cog_policy_gae(const cog_gae_args *a) {
+  auto bad = [&](const std::string &msg) { return fail(COG_ERR_INVALID, "policy_gae: " + msg); };
+  if (!a) return fail(COG_ERR_INVALID, "NULL argument");
+  if (a->stream == COG_NO_STREAM) return bad("COG_NO_STREAM: it runs on the caller's stream (NULL is the null stream)");
+  if (a->device < 0) return bad("device ordinal " + std::to_string(a->device) + " out of range");
+  if (!a->T || !a->n) return COG_OK;
+  if (a->n > (size_t)0x7fffffffu * 64) return bad("n " + std::to_string(a->n) + " is more than one launch covers");
+  if (!a->d_values) return bad("values pointer is NULL");
+  if (!a->d_agents) return bad("agents pointer is NULL");
+  if (!a->d_rewards) return bad("rewards pointer is NULL");
+  if (!a->d_dones) return bad("dones pointer is NULL");
+  if (!a->d_advantages || !a->d_returns) return bad("advantages / returns pointer is NULL");
+  if (a->values_ld < a->n) return bad("values_ld " + std::to_string(a->values_ld) + " < n: the row stride is less than a row");
+  if (a->agents_ld < a->n) return bad("agents_ld " + std::to_string(a->agents_ld) + " < n: the row stride is less than a row");
+  if (a->dones_ld < a->n) return bad("dones_ld " + std::to_string(a->dones_ld) + " < n: the row stride is less than a row");
+  if (a->rewards_ld < 4 * a->n)
+    return bad("rewards_ld " + std::to_string(a->rewards_ld) + " < 4 n: the row stride is less than a row");
+  if (a->rewards_ld % 4 || reinterpret_cast<uintptr_t>(a->d_rewards) % 16)
+    return bad("reward rows must be 16-byte aligned (pointer, and a row stride that is a multiple of 4 floats)");
+  if (reinterpret_cast<uintptr_t>(a->d_values) % 4 || reinterpret_cast<uintptr_t>(a->d_last_values) % 4 ||
+      reinterpret_cast<uintptr_t>(a->d_advantages) % 4 || reinterpret_cast<uintptr_t>(a->d_returns) % 4)
+    return bad("values / last_values / advantages / returns pointer is not aligned to float");
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
+    return fail(COG_ERR_NODEVICE, "no HIP device available (the engine has no CPU fallback)");
+  if (a->device >= count) return bad("device ordinal " + std::to_string(a->device) + " out of range");
+  cog::TurnGae p{};
+  p.T = a->T;
+  p.n = a->n;
+  p.values = a->d_values;
+  p.values_ld = a->values_ld;
+  p.agents = a->d_agents;
+  p.agents_ld = a->agents_ld;
+  p.rewards = a->d_rewards;
+  p.rewards_ld = a->rewards_ld;
+  p.dones = a->d_dones;
+  p.dones_ld = a->dones_ld;
+  p.last_values = a->d_last_values;
+  p.gamma = a->gamma;
+  p.lam = a->lam;
+  p.advantages = a->d_advantages;
+  p.returns = a->d_returns;
+  DeviceGuard g(a->device);
+  if (cog::launch_turn_gae(p, a->stream))
+    return fail(COG_ERR_HIP, std::string("policy_gae launch failed: ") + hipGetErrorString(hipGetLastError()));
+  return COG_OK;
+}
+
 int cog_sampler_sample(cog_sampler *s, const cog_action_mask_t *masks, size_t n) {
   if (!s || (!masks && n)) return fail(COG_ERR_INVALID, "NULL argument");
   if (n != s->n) return fail(COG_ERR_INVALID, "action_mask length != num_envs");

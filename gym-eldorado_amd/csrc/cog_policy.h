@@ -1,7 +1,8 @@
 // cog_policy.h -- internal interface between the C-ABI layer (cog_abi.cpp) and the policy sampler
 // kernels (cog_policy.hip): masked categorical actions from a batch of logits, and the evaluator of
-// recorded actions under new logits with its gradient.  Not part of the public ABI (include/cog.h
-// cog_sampler_sample_policy, cog_policy_evaluate and cog_policy_evaluate_backward are).
+// recorded actions under new logits with its gradient, and the per-seat advantage estimator.  Not
+// part of the public ABI (include/cog.h cog_sampler_sample_policy, cog_policy_evaluate,
+// cog_policy_evaluate_backward and cog_policy_gae are).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -44,5 +45,24 @@ struct PolicyEval {
 
 // the forward or the backward kernel; 0, or -1 when the launch failed; n == 0 launches nothing
 int launch_policy_eval(const PolicyEval &p, bool backward, void *stream);
+
+// per-seat advantage estimation over a time-major window (include/cog.h cog_policy_gae)
+struct TurnGae {
+  size_t T, n;                       // rows, envs
+  const float *values;               // [T] rows of n, values_ld floats apart (>= n)
+  size_t values_ld;
+  const uint8_t *agents;             // [T] rows of n seat bytes (low two bits), agents_ld bytes apart
+  size_t agents_ld;
+  const float *rewards;              // [T] rows of n x 4, rewards_ld floats apart (>= 4 n)
+  size_t rewards_ld;
+  const uint8_t *dones;              // [T] rows of n bytes (!= 0: done), dones_ld bytes apart
+  size_t dones_ld;
+  const float *last_values;          // [n][4], or null = zeros
+  float gamma, lam;
+  float *advantages, *returns;       // [T][n] contiguous
+};
+
+// 0, or -1 when the launch failed; T == 0 or n == 0 launches nothing
+int launch_turn_gae(const TurnGae &p, void *stream);
 
 }  // namespace cog

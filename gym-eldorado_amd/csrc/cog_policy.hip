@@ -26,7 +26,8 @@
 // head and leaves the sampler's state alone.
 //
 // The policy evaluator (cog_policy_evaluate and its backward, further down) shares the staging code
-// and the shape.
+// and the shape.  The advantage estimator (cog_policy_gae, at the end) is a kernel of its own shape:
+// one lane per (env, seat) walking the rows of a rollout window.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -554,7 +555,97 @@ __global__ void __launch_bounds__(kTile *kWaves) k_policy_eval_backward(EvalArgs
   }
 }
 
+// ---- per-seat advantage estimation (include/cog.h cog_policy_gae) -------------------------------
+// One lane per (env, seat): lane 4 i + p walks env i's rows from T - 1 down to 0 with seat p's three
+// scalars (next value, advantage at its next own row, pending reward) in registers, so no state is
+// selected by a runtime seat index.  The lanes of a wave read rewards[t] as one contiguous run of
+// floats; the four lanes of an env read the same values / agents / dones element, and the lane whose
+// seat acts at row t stores the two outputs.  A row's addresses do not depend on the recursion, so
+// the loads of kGaeRows rows are issued ahead of the chain, which is a few multiplies and adds per
+// row (not contracted: the library is built with -ffp-contract=off); the rows left over at the bottom
+// of the window go through the same batch with the row index clamped into the window and the
+// arithmetic skipped, not through a loop of dependent single-row loads.  No atomics, no LDS: the
+// same inputs give the same bits.  8 rows ahead in workgroups of 256 measured fastest of 4 / 8 / 16 /
+// 24 / 32 rows x 64 / 128 / 256 threads at every shape: from 16 rows on the row
+// bases no longer fit the scalar registers (40 of them spill at 16 rows, 223 at 32).
+
+constexpr int kGaeRows = 8;                                // rows loaded ahead of the chain
+constexpr int kGaeBlock = 256;                             // threads per workgroup: 64 envs
+
+struct GaeArgs {
+  size_t T, n;
+  const float *values;
+  size_t values_ld;
+  const uint8_t *agents;
+  size_t agents_ld;
+  const float *rewards;
+  size_t rewards_ld;                                       // floats
+  const uint8_t *dones;
+  size_t dones_ld;
+  const float *last_values;                                // [n][4], or null: zeros
+  float gamma, lam;
+  float *advantages, *returns;                             // row stride n
+};
+
+struct GaeSeat {
+  float nv, adv, rew;                                      // next value, next own advantage, pending reward
+};
+
+// rows top, top - 1, .. (cnt of them; FULL: kGaeRows) of env i for the lane of seat p (g = 4 i + p)
+template <bool FULL>
+DEV void gae_rows(const GaeArgs &a, size_t top, int cnt, size_t i, size_t g, uint32_t p, float gl, GaeSeat &s) {
+  float v[kGaeRows], r[kGaeRows];
+  uint32_t ag[kGaeRows], dn[kGaeRows];
+#pragma unroll
+  for (int k = 0; k < kGaeRows; k++) {
+    const size_t t = FULL || k < cnt ? top - (size_t)k : 0;   // (a row of the window in any case)
+    v[k] = a.values[t * a.values_ld + i];
+    ag[k] = a.agents[t * a.agents_ld + i];
+    dn[k] = a.dones[t * a.dones_ld + i];
+    r[k] = a.rewards[t * a.rewards_ld + g];
+  }
+#pragma unroll
+  for (int k = 0; k < kGaeRows; k++) {
+    if (FULL || k < cnt) {
+      if (dn[k] != 0u) {                                   // (the only use of a reward: elsewhere it may be NaN)
+        s.nv = 0.0f;
+        s.adv = 0.0f;
+        s.rew = r[k];
+      }
+      if ((ag[k] & 3u) == p) {
+        const float delta = s.rew + a.gamma * s.nv - v[k];
+        s.adv = delta + gl * s.adv;
+        const size_t o = (top - (size_t)k) * a.n + i;
+        a.advantages[o] = s.adv;
+        a.returns[o] = s.adv + v[k];
+        s.nv = v[k];
+        s.rew = 0.0f;
+      }
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kGaeBlock) k_turn_gae(GaeArgs a) {
+  const size_t g = (size_t)blockIdx.x * kGaeBlock + threadIdx.x, i = g >> 2;
+  if (i >= a.n) return;
+  const uint32_t p = (uint32_t)g & 3u;
+  GaeSeat s{a.last_values ? a.last_values[g] : 0.0f, 0.0f, 0.0f};
+  const float gl = a.gamma * a.lam;
+  size_t left = a.T;                                       // rows 0 .. left - 1 are still to do
+  for (; left >= (size_t)kGaeRows; left -= kGaeRows) gae_rows<true>(a, left - 1, kGaeRows, i, g, p, gl, s);
+  if (left) gae_rows<false>(a, left - 1, (int)left, i, g, p, gl, s);
+}
+
 }  // namespace
+
+int launch_turn_gae(const TurnGae &p, void *stream) {
+  if (!p.T || !p.n) return 0;
+  const GaeArgs a{p.T,     p.n,        p.values,      p.values_ld, p.agents, p.agents_ld,  p.rewards, p.rewards_ld,
+                  p.dones, p.dones_ld, p.last_values, p.gamma,     p.lam,    p.advantages, p.returns};
+  const dim3 grid((unsigned)((4 * p.n + kGaeBlock - 1) / kGaeBlock));
+  hipLaunchKernelGGL(k_turn_gae, grid, dim3(kGaeBlock), 0, (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 
 int launch_policy_eval(const PolicyEval &p, bool backward, void *stream) {
   if (!p.n) return 0;

@@ -390,6 +390,37 @@ PYBIND11_MODULE(_city_of_gold, m) {
       "stream"_a = 0, "backward"_a = false,
       "log-probability and entropy of recorded actions under new logits, or (backward=True) their gradient");
   m.def(
+      "policy_gae_raw",
+      [](size_t T, size_t n, uintptr_t d_values, size_t values_ld, uintptr_t d_agents, size_t agents_ld, uintptr_t d_rewards,
+         size_t rewards_ld, uintptr_t d_dones, size_t dones_ld, uintptr_t d_last_values, float gamma, float lam,
+         uintptr_t d_advantages, uintptr_t d_returns, int device, int64_t stream) {
+        // cog_policy_gae over raw device pointers (city_of_gold turn_gae is the torch face); stream a
+        // hipStream_t handle (0 = the null stream; -1: none, which is refused)
+        cog_gae_args a{};
+        a.T = T;
+        a.n = n;
+        a.d_values = reinterpret_cast<const float *>(d_values);
+        a.values_ld = values_ld;
+        a.d_agents = reinterpret_cast<const uint8_t *>(d_agents);
+        a.agents_ld = agents_ld;
+        a.d_rewards = reinterpret_cast<const float *>(d_rewards);
+        a.rewards_ld = rewards_ld;
+        a.d_dones = reinterpret_cast<const uint8_t *>(d_dones);
+        a.dones_ld = dones_ld;
+        a.d_last_values = reinterpret_cast<const float *>(d_last_values);
+        a.gamma = gamma;
+        a.lam = lam;
+        a.d_advantages = reinterpret_cast<float *>(d_advantages);
+        a.d_returns = reinterpret_cast<float *>(d_returns);
+        a.device = device;
+        a.stream = stream < 0 ? COG_NO_STREAM : reinterpret_cast<void *>((uintptr_t)stream);
+        check(cog_policy_gae(&a));
+      },
+      "T"_a, "n"_a, "d_values"_a, "values_ld"_a, "d_agents"_a, "agents_ld"_a, "d_rewards"_a, "rewards_ld"_a, "d_dones"_a,
+      "dones_ld"_a, "d_last_values"_a = 0, "gamma"_a = 0.99f, "lam"_a = 0.95f, "d_advantages"_a = 0, "d_returns"_a = 0,
+      "device"_a = 0, "stream"_a = 0,
+      "per-seat generalised advantage estimation over a time-major window of a turn-based rollout");
+  m.def(
       "time_stream_mix",
       [](int device, size_t bytes, int iters) {
         double gbs = 0.0;

@@ -268,6 +268,42 @@ typedef struct cog_policy_eval_args {
 } cog_policy_eval_args;
 COG_API int cog_policy_evaluate(const cog_policy_eval_args *a);            /* forward  */
 COG_API int cog_policy_evaluate_backward(const cog_policy_eval_args *a);   /* backward */
+/* Per-seat generalised advantage estimation (an addition) over a time-major window of a turn-based
+ * rollout: rows t = 0..T-1, envs i = 0..n-1.
+ *   a = agents[t,i] & 3 is the seat whose action row t holds (agent_selection BEFORE step t);
+ *   v = values[t,i] is that seat's value estimate at that state;
+ *   dones[t,i] (a byte != 0 is done) and rewards[t,i,0..3] are the env's views AFTER step t.
+ * rewards[t,i,:] is used only where dones[t,i] != 0 (the rewards view is stale between dones):
+ * anywhere else it may hold anything, NaN included, without effect.  A done of any kind ends the
+ * episode (a turn limit is not told from a win), and the row after it belongs to a new episode.
+ * Each env keeps three numbers per seat p, walking t from T-1 down to 0: nv[p], the seat's next
+ * value, starting at last_values[i,p] (0 when d_last_values is NULL): seat p's value at the state
+ * after the last row; A[p], the advantage at the seat's next own row, starting at 0; R[p], the
+ * reward pending for the seat, starting at 0.  At row t:
+ *   1. if dones[t,i]: for all four seats, nv[p] = 0; A[p] = 0; R[p] = rewards[t,i,p];
+ *   2. for a only: delta = R[a] + gamma nv[a] - v; A[a] = delta + gamma lam A[a];
+ *      advantages[t,i] = A[a]; returns[t,i] = A[a] + v; nv[a] = v; R[a] = 0.
+ * So gamma discounts per own decision of a seat, not per env row; the terminal reward lands
+ * undiscounted on each seat's last row of the episode; a seat with no row in an episode contributes
+ * nothing, and seats >= n_players never act.  This equals textbook GAE run on each seat's own rows
+ * of each episode, bootstrapped with 0 after a done and with last_values at the window's end.
+ * Rows of values / agents / dones are values_ld / agents_ld / dones_ld elements apart (>= n), rows
+ * of rewards rewards_ld floats apart (>= 4 n, a multiple of 4, d_rewards 16-byte aligned);
+ * d_last_values is n x 4 contiguous; the outputs are T x n contiguous.  float32 arithmetic, no
+ * atomics: the same inputs give the same bits.  One kernel on `stream` of `device`; it does not wait
+ * on the host, and COG_NO_STREAM is refused.  T == 0 or n == 0 launches nothing. */
+typedef struct cog_gae_args {
+  size_t T, n;
+  const float *d_values; size_t values_ld;
+  const uint8_t *d_agents; size_t agents_ld;
+  const float *d_rewards; size_t rewards_ld;               /* in floats                              */
+  const uint8_t *d_dones; size_t dones_ld;
+  const float *d_last_values;                              /* may be NULL: zeros                     */
+  float gamma, lam;
+  float *d_advantages; float *d_returns;                   /* T rows of n, row stride n              */
+  int device; void *stream;                                /* device ordinal; caller's hipStream_t (NULL: the null stream) */
+} cog_gae_args;
+COG_API int cog_policy_gae(const cog_gae_args *a);
 COG_API cog_action_t *cog_sampler_actions(cog_sampler *s);   /* persistent host view */
 COG_API void *cog_sampler_device_actions(cog_sampler *s);    /* device view (shard 0) */
 COG_API void *cog_sampler_shard_device_actions(cog_sampler *s, int shard);

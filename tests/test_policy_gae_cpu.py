@@ -1,0 +1,127 @@
+"""CPU: the advantage estimator's surface (header, library, Python functions) and the numpy
+reference's own checks: the recursion of include/cog.h equals the per-episode, per-seat textbook
+form, ignores every reward outside a done row, and its float32 mode pins the tolerance that
+tests/test_gpu_policy_gae.py allows the kernel."""
+import ctypes
+import os
+import re
+
+import numpy as np
+
+import gae_ref as gr
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LIB = os.path.join(ROOT, "gym-eldorado_amd", "city_of_gold", "libcog_hip.so")
+
+
+def test_header_declares_the_advantage_estimator():
+    src = open(os.path.join(ROOT, "include", "cog.h")).read()
+    assert re.search(r"COG_API\s+int\s+cog_policy_gae\s*\(\s*const\s+cog_gae_args\s*\*", src)
+    m = re.search(r"typedef struct cog_gae_args \{(.*?)\} cog_gae_args;", src, re.S)
+    assert m
+    for field in ("size_t T, n;", "const float *d_values;", "size_t values_ld;", "const uint8_t *d_agents;",
+                  "size_t agents_ld;", "const float *d_rewards;", "size_t rewards_ld;", "const uint8_t *d_dones;",
+                  "size_t dones_ld;", "const float *d_last_values;", "float gamma, lam;", "float *d_advantages;",
+                  "float *d_returns;", "int device;", "void *stream;"):
+        assert field in m.group(1), field
+    assert re.search(r"#define\s+COG_ABI_VERSION\s+1\b", src)
+
+
+def test_null_arguments_are_invalid():
+    lib = ctypes.CDLL(LIB)
+    lib.cog_last_error.restype = ctypes.c_char_p
+    lib.cog_policy_gae.restype = ctypes.c_int
+    lib.cog_policy_gae.argtypes = [ctypes.c_void_p]
+    assert lib.cog_policy_gae(None) == -1                               # COG_ERR_INVALID
+    assert b"NULL" in lib.cog_last_error()
+    assert lib.cog_abi_version() == 1
+
+
+def test_python_functions_exist(cg):
+    assert callable(cg.turn_gae)
+    assert "turn_gae" in cg.__all__ and "turn_gae" in cg.__doc__
+    assert callable(cg._C.policy_gae_raw)
+
+
+def random_windows():
+    rng = np.random.default_rng(53)
+    for T, n, p in ((1, 5, 0.5), (2, 40, 0.5), (3, 40, 0.3), (17, 64, 0.1), (64, 100, 0.05), (64, 30, 0.0),
+                    (200, 20, 0.02), (512, 12, 0.004), (40, 300, 1.0)):
+        yield gr.window(rng, T, n, p)
+
+
+def test_scan_equals_the_brute_force_definition():
+    for w in random_windows():
+        for gamma, lam in gr.PARAMS:
+            for last in (w["last_values"], None):
+                a, r = gr.scan(*gr.arrays(w), last, gamma, lam)
+                b, s = gr.brute(*gr.arrays(w), last, gamma, lam)
+                assert np.abs(a - b).max() <= 1e-12 and np.abs(r - s).max() <= 1e-12, (w["values"].shape, gamma, lam)
+
+
+def test_rewards_outside_done_rows_have_no_effect():
+    """NaN in every non-done reward row (the generator's own), then 1e30 there: the outputs are finite
+    and the same bits."""
+    for w in random_windows():
+        assert np.isnan(w["rewards"][w["dones"] == 0]).all()
+        a, r = gr.scan(*gr.arrays(w), w["last_values"])
+        assert np.isfinite(a).all() and np.isfinite(r).all()
+        other = np.where(np.isnan(w["rewards"]), np.float32(1e30), w["rewards"])
+        a2, r2 = gr.scan(w["values"], w["agents"], other, w["dones"], w["last_values"])
+        assert np.array_equal(a, a2) and np.array_equal(r, r2)
+
+
+def test_hand_written_window():
+    """One env, agents 0,0,1,0,1,1, a done at row 3, gamma = lam = 0.5 (the numbers of
+    tests/test_gpu_policy_gae.py, worked by hand)."""
+    values = np.array([1, 2, 3, 4, 5, 6], dtype=np.float32)[:, None]
+    agents = np.array([0, 0, 1, 0, 1, 1], dtype=np.uint8)[:, None]
+    dones = np.array([0, 0, 0, 1, 0, 0], dtype=np.uint8)[:, None]
+    rewards = np.full((6, 1, 4), np.nan, dtype=np.float32)
+    rewards[3, 0] = (10, 20, 30, 40)
+    last = np.array([[7, 8, 9, 10]], dtype=np.float32)
+    for fn in (gr.scan, gr.brute):
+        a, r = fn(values, agents, rewards, dones, last, 0.5, 0.5)
+        assert a[:, 0].tolist() == [0.375, 1.5, 17.0, 6.0, -2.5, -2.0]
+        assert r[:, 0].tolist() == [1.375, 3.5, 20.0, 10.0, 2.5, 4.0]
+
+
+def test_gpu_windows_hold_their_cases():
+    seen = {}
+    for T, n in gr.SHAPES:
+        for k, v in gr.features(gr.case(T, n)).items():
+            seen[k] = seen.get(k, False) or v
+    assert all(seen.values()), seen
+    big = gr.features(gr.case(128, 300))                                # one window holds all of them at once
+    assert all(big.values()), big
+
+
+def test_oracle_window_meets_the_recorded_tests_conditions():
+    for players in (4, 3, 2):
+        gr.check_oracle_window(gr.oracle_window(players), players)
+
+
+def test_exact_case_is_exact():
+    """gamma = lam = 1 on integers in [-8, 8]: float32 equals float64 bit for bit, |A| < 2^24."""
+    for T, n in ((512, 64), (128, 300), (9, 65)):
+        w = gr.case(T, n, integers=True)
+        a64, r64 = gr.scan(*gr.arrays(w), w["last_values"], 1.0, 1.0)
+        a32, r32 = gr.scan(*gr.arrays(w), w["last_values"], 1.0, 1.0, dtype=np.float32)
+        assert a32.dtype == np.float32 and np.array_equal(a32, a64) and np.array_equal(r32, r64)
+        assert max(np.abs(a64).max(), np.abs(r64).max()) < 2 ** 24
+
+
+def test_float32_mode_pins_the_gpu_tolerance():
+    """The largest |float32 - float64| of the recursion over every input the GPU tests compare within
+    TOL: gae_ref.MEASURED_F32_DEVIATION is that figure (rounded up, to two digits), TOL 4 times it."""
+    worst, biggest = 0.0, 0.0
+    for label, args, kw in gr.all_gpu_inputs():
+        a64, r64 = gr.scan(*args, **kw)
+        a32, r32 = gr.scan(*args, dtype=np.float32, **kw)
+        assert a32.dtype == np.float32 and np.isfinite(a64).all() and np.isfinite(r64).all()
+        dev = max(np.abs(a32 - a64).max(), np.abs(r32 - r64).max())
+        print(f"{label}: float32 against float64 {dev:.3g}, max |adv| {np.abs(a64).max():.3g}")
+        worst, biggest = max(worst, dev), max(biggest, np.abs(a64).max())
+    print(f"largest deviation {worst:.4g} (max |adv| {biggest:.3g}); MEASURED_F32_DEVIATION {gr.MEASURED_F32_DEVIATION:.4g}")
+    assert worst <= gr.MEASURED_F32_DEVIATION <= 1.05 * worst
+    assert gr.TOL == 4 * gr.MEASURED_F32_DEVIATION
