@@ -17,7 +17,8 @@
 //   cgrid [N] x 2304 B    compact 48x48 hex-code grid of the final map in observation cell order
 //                         (the lookup table of movement masks / done checks, and the source of
 //                         the map-observation encode)
-//   gen   [N] x 256 B     map-generation scratch (pieces list, per-env piece transforms)
+//   gen   [N] x 4288 B    map-generation scratch (pieces list, per-env piece transforms, the list of
+//                         hexes of a map that left the lattice)
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -30,8 +31,11 @@ constexpr int kGridDim = 128;
 constexpr int kGridOff = 64;
 constexpr int kGridBytes = kGridDim * kGridDim;
 #define COG_CELLS 2304                // 48 * 48
-constexpr int kMaxCoord = 62;        // |x|,|y| of any placed hex; beyond -> hazard GRID_OVER
+// what the wave's generation can hold; past either it gives up (MAPGEN_FAIL: the reference, unbounded,
+// goes on, and in every such generation seen it ends without a map; GRID_OVER is finalize's check alone)
+constexpr int kMaxCoord = 62;        // |x|,|y| of any placed hex
 constexpr int kMaxPlaced = 96;       // pieces placed in one generation (incl. recursion)
+constexpr int kMaxOff = 1008;        // hexes placed from the first piece off the lattice on
 
 // hazard / status flags (same bit meaning as the oracle's ORC_F_*)
 constexpr uint32_t F_MAPGEN_FAIL = 0x01u;
@@ -80,8 +84,9 @@ struct alignas(64) GenScratch {
   int16_t pcx[20], pcy[20];          // piece centres (doubled coords)
   uint8_t prot[20];                  // piece rotations mod 6
   uint8_t npieces, pad[11];
+  uint8_t off[kMaxOff][4];           // hexes of a map that left the lattice: doubled x, y, code (cog_engine.hip GenW)
 };
-static_assert(sizeof(GenScratch) <= 256, "GenScratch");
+static_assert(sizeof(GenScratch) <= 256 + 4 * kMaxOff, "GenScratch");
 
 struct DevState {
   size_t n;

@@ -807,10 +807,28 @@ DEV int conn_set_id(int q, int psize) {
   return (qs == COG_PS_SMALL && psize == COG_PS_LARGE) ? 3 : -1;
 }
 
+// how a generation ends without a map, beside running out of attempts: the finished map is wider
+// than the observation (finalize's check: the reference's and the oracle's GRID_OVER), or a piece
+// left what the engine can hold (kMaxCoord, kMaxPlaced, kMaxOff).  The reference has no such bound
+// and goes on; the maps seen past it all end without a map (big maps), so the engine
+// gives up there as it does after its bounded attempts: MAPGEN_FAIL, never a write outside the grid
+enum { kGenRun = 0, kGenWide = 1, kGenBound = 2 };
+// Hexes off the lattice.  A travel piece for which no placement is free stays reset at the origin
+// while the list of placed pieces may still name it; connection points taken from a small piece
+// there lie half a cell off the map's lattice, and so does every piece connected through them
+// (doubled coordinates with an odd component).  Such a hex coincides with no hex of the grid.  From
+// the first such piece on, every placed hex also goes, in the reference's order, into a list
+// (GenScratch::off: doubled x, doubled y, code): candidates off the lattice are tested against it,
+// and the cell grid takes the list's hexes after the grid's, in order, as hex_array and finalize
+// write the cells of the map in list order (a later hex wins a cell two of them fall into).
 struct GenW {                         // wave-uniform generation state of one env
   uint8_t *grid;
-  int minx, miny, maxx, maxy, dimx, dimy;
+  uint8_t (*off)[4];                  // the list, noff entries; offmode: placements append to it
+  int noff, offmode;
+  int lo2x, lo2y, hi2x, hi2y;         // Map::min_xy / max_xy in doubled coordinates, every hex
+  int minx, miny, maxx, maxy, dimx, dimy;   // minx..maxy: the box of the hexes in the grid
   uint32_t flags;                     // EnvPriv::flags (sticky: read at entry, written back)
+  int stop;                           // why this generation ended early (kGen*); an earlier one's flags decide nothing
   int np;                             // pieces placed
   int pl0, pl1;                       // lane k: pieces[k], pieces[64 + k]
   int tx, ty, tr;                     // lane q < COG_N_PIECES: pcx[q], pcy[q], prot[q]
@@ -821,6 +839,8 @@ DEV void coop_map_reset(GenW &W) {                         // map.cpp:744-752
   for (int x = W.minx; x <= W.maxx; x++)
     for (int y = W.miny + lane_id(); y <= W.maxy; y += 64) W.grid[(x + kGridOff) * kGridDim + (y + kGridOff)] = 0;
   W.minx = W.miny = W.maxx = W.maxy = 0;
+  W.lo2x = W.lo2y = W.hi2x = W.hi2y = 0;
+  W.noff = W.offmode = 0;
   W.dimx = W.dimy = 0;
   W.np = 0;
   wg_fence();
@@ -840,7 +860,7 @@ DEV bool coop_add_piece(GenW &W, int p, int cx2, int cy2, int rot) {
     W.ty = pcy;
   }
   if (W.np >= kMaxPlaced) {
-    W.flags |= F_GRID_OVER;
+    W.stop = kGenBound;
     return false;
   }
   if (W.np < 64) {
@@ -856,20 +876,50 @@ DEV bool coop_add_piece(GenW &W, int p, int cx2, int cy2, int rot) {
   const RotUV R = rot_uv(r);
   const int rx = X * R.ux + Y * R.vx + pcx, ry = X * R.uy + Y * R.vy + pcy;
   const int x = rx >> 1, y = ry >> 1;                      // exact: only used when both are even
-  const bool bad = ((rx | ry) & 1) || x < -kMaxCoord || x > kMaxCoord || y < -kMaxCoord || y > kMaxCoord;
+  const bool odd = (rx | ry) & 1;                          // (the same for every hex of the piece)
+  constexpr int kMax2 = 2 * kMaxCoord + 1;
+  const bool bad = rx < -kMax2 || rx > kMax2 || ry < -kMax2 || ry > kMax2;
   const uint64_t bm = __builtin_amdgcn_ballot_w64(in && bad);
   const int f = bm ? __ffsll((unsigned long long)bm) - 1 : nh;
-  if (lane < f) W.grid[(x + kGridOff) * kGridDim + (y + kGridOff)] = c_phex[p][lane];
+  if (__builtin_amdgcn_ballot_w64(in && odd)) W.offmode = 1;
+  const bool full = W.offmode && W.noff + nh > kMaxOff;
+  if (lane < f && !odd) W.grid[(x + kGridOff) * kGridDim + (y + kGridOff)] = c_phex[p][lane];
+  if (lane < f && W.offmode && !full) {
+    uint8_t *o = W.off[W.noff + lane];
+    o[0] = (uint8_t)(int8_t)rx; o[1] = (uint8_t)(int8_t)ry; o[2] = c_phex[p][lane];
+  }
   wg_fence();
-  if (bm) {
-    W.flags |= F_GRID_OVER;
+  if (bm || full) {
+    W.stop = kGenBound;
     return false;
   }
-  W.minx = min(W.minx, wave_min(in ? x : W.minx));
-  W.miny = min(W.miny, wave_min(in ? y : W.miny));
-  W.maxx = max(W.maxx, wave_max(in ? x : W.maxx));
-  W.maxy = max(W.maxy, wave_max(in ? y : W.maxy));
+  if (W.offmode) W.noff += nh;
+  W.lo2x = min(W.lo2x, wave_min(in ? rx : W.lo2x));
+  W.lo2y = min(W.lo2y, wave_min(in ? ry : W.lo2y));
+  W.hi2x = max(W.hi2x, wave_max(in ? rx : W.hi2x));
+  W.hi2y = max(W.hi2y, wave_max(in ? ry : W.hi2y));
+  if (!odd) {                                              // (wave-uniform)
+    W.minx = min(W.minx, wave_min(in ? x : W.minx));
+    W.miny = min(W.miny, wave_min(in ? y : W.miny));
+    W.maxx = max(W.maxx, wave_max(in ? x : W.maxx));
+    W.maxy = max(W.maxy, wave_max(in ? y : W.maxy));
+  }
   return true;
+}
+
+// this lane's candidate lies off the lattice and one of its hexes is in the list
+template <int NH>
+DEV bool off_hit(const GenW &W, const int8_t (*xy)[2], int t, int cx2, int cy2) {
+  const RotUV R = rot_uv(t);
+  const int X0 = xy[0][0], Y0 = xy[0][1];
+  if (!((X0 * R.ux + Y0 * R.vx + cx2) & 1) && !((X0 * R.uy + Y0 * R.vy + cy2) & 1)) return false;   // on the lattice: the grid knows
+  for (int k = 0; k < NH; k++) {
+    const int X = xy[k][0], Y = xy[k][1];
+    const int rx = X * R.ux + Y * R.vx + cx2, ry = X * R.uy + Y * R.vy + cy2;
+    for (int j = 0; j < W.noff; j++)
+      if ((int)(int8_t)W.off[j][0] == rx && (int)(int8_t)W.off[j][1] == ry) return true;
+  }
+  return false;
 }
 
 // footprint_free for this lane's candidate: every hex's grid load issued before any is used
@@ -941,6 +991,11 @@ DEV bool cand_free(const GenW &W, int p, int psize, int c, int total) {
   if (psize == COG_PS_LARGE) hit = footprint_hit<37>(W.grid, kLargeXY, t, cx, cy);
   else if (psize == COG_PS_SMALL) hit = footprint_hit<16>(W.grid, kSmallXY, t, cx, cy);
   else hit = footprint_hit<3>(W.grid, kEndXY, t, cx, cy);
+  if (W.noff && !hit && c < total) {
+    if (psize == COG_PS_LARGE) hit = off_hit<37>(W, kLargeXY, t, cx, cy);
+    else if (psize == COG_PS_SMALL) hit = off_hit<16>(W, kSmallXY, t, cx, cy);
+    else hit = off_hit<3>(W, kEndXY, t, cx, cy);
+  }
   if (c >= total) return false;
   return !hit;
 }
@@ -992,9 +1047,10 @@ DEV bool coop_add_random_piece(GenW &W, int p, uint32_t &rng) {
 }
 
 DEV bool coop_finalize_ok(GenW &W) {                       // map.cpp:389-405 (dims check, Q27)
-  const int dx = 3 + W.maxx - W.minx, dy = 3 + W.maxy - W.miny;
+  const int dx = 3 + ((W.hi2x - W.lo2x) >> 1), dy = 3 + ((W.hi2y - W.lo2y) >> 1);   // (long)(3 + max - min)
   if (dx > 49 || dy > 49) {
     W.flags |= F_GRID_OVER;
+    W.stop = kGenWide;
     return false;
   }
   W.dimx = dx;
@@ -1049,7 +1105,7 @@ DEV bool coop_generate_frames(GenW &W, uint32_t rng0, int n_pieces, int diff) {
         if (nv) {
           next = (int)nth_set_bit(mask, uid(rng, nv));
           ok = coop_add_random_piece(W, COG_PIECE_TRAVEL0 + next, rng);
-          if (W.flags & F_GRID_OVER) return false;
+          if (W.stop) return false;
         }
         fi++;
         if (ok) {                                          // vector::erase(begin() + next), Q5
@@ -1066,7 +1122,7 @@ DEV bool coop_generate_frames(GenW &W, uint32_t rng0, int n_pieces, int diff) {
       const uint32_t en = uid(rng, 2);
       stage = FIN;
       const bool ok = coop_add_random_piece(W, COG_PIECE_END0 + (int)en, rng);
-      if (W.flags & F_GRID_OVER) return false;
+      if (W.stop) return false;
       if (!ok) {
         coop_map_reset(W);
         if (depth + 1 >= COG_MAX_FAILURES) return false;
@@ -1091,18 +1147,31 @@ DEV bool coop_generate_frames(GenW &W, uint32_t rng0, int n_pieces, int diff) {
   return true;
 }
 
+// Map::min_xy as the cells of hexes with integer coordinates see it: (long)(x - min + 1) with a
+// half-integer min is x - ceil(min) + 1
+DEV int ceil_half(int v2) { return (v2 + 1) >> 1; }
 DEV void coop_build_cgrid(const GenW &W, uint8_t *cgrid) {  // build_cgrid, lane k: block k
   uint4 *out = reinterpret_cast<uint4 *>(cgrid);
+  const int minx = ceil_half(W.lo2x), miny = ceil_half(W.lo2y);
   for (int k = lane_id(); k < kEncBlocks; k += 64) {
     const int ix = k / 3, iy0 = (k % 3) * 16;
     uint32_t w[4] = {0u, 0u, 0u, 0u};
     if (ix < W.dimx) {
-      const uint8_t *row = W.grid + (ix - 1 + W.minx + kGridOff) * kGridDim + kGridOff + W.miny - 1;
+      const uint8_t *row = W.grid + (ix - 1 + minx + kGridOff) * kGridDim + kGridOff + miny - 1;
 #pragma unroll
       for (int j = 0; j < 16; j++)
         if (iy0 + j < W.dimy) w[j >> 2] |= (uint32_t)row[iy0 + j] << (8 * (j & 3));
     }
     out[k] = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+  if (W.noff) {                                            // the list's hexes, in order, over the grid's
+    wg_fence();
+    if (lane_id() == 0)
+      for (int j = 0; j < W.noff; j++) {
+        const int ix = (((int)(int8_t)W.off[j][0] - W.lo2x) >> 1) + 1, iy = (((int)(int8_t)W.off[j][1] - W.lo2y) >> 1) + 1;
+        cgrid[ix * COG_GRID + iy] = W.off[j][2];
+      }
+    wg_fence();
   }
 }
 
@@ -1129,6 +1198,8 @@ DEV bool coop_generate(const DevState &s, uint32_t env, int owner, const GenIn &
   W.maxx = (int8_t)((bounds >> 16) & 0xffu); W.maxy = (int8_t)(bounds >> 24);
   W.dimx = W.dimy = 0;
   W.flags = (uint32_t)rdl((int)own.flags, owner);
+  W.stop = kGenRun;
+  W.off = gs->off;
   const uint32_t rng0 = (uint32_t)rdl((int)own.rng, owner);
   const uint32_t npd = (uint32_t)rdl((int)own.npd, owner);
   const int n_pieces = (int)(npd & 0xffu), diff = (int)(npd >> 8);
@@ -1137,8 +1208,11 @@ DEV bool coop_generate(const DevState &s, uint32_t env, int owner, const GenIn &
   W.pl0 = W.pl1 = 0;
   const bool ok = coop_generate_frames(W, rng0, n_pieces, diff);
   if (ok) coop_build_cgrid(W, s.cgrid + (size_t)env * COG_CELLS);
+  else if (W.stop != kGenWide) W.flags |= F_MAPGEN_FAIL;   // generate_map_failure (map.cpp:699-702); finalize's GRID_OVER alone otherwise, as the oracle flags it
   if (lane == owner) {                                     // what the owner lane reads back later
-    pv->minx = (int8_t)W.minx; pv->miny = (int8_t)W.miny; pv->maxx = (int8_t)W.maxx; pv->maxy = (int8_t)W.maxy;
+    // (what the lookups subtract, and a box that holds every hex of the grid for the next map_reset)
+    pv->minx = (int8_t)ceil_half(W.lo2x); pv->miny = (int8_t)ceil_half(W.lo2y);
+    pv->maxx = (int8_t)(W.hi2x >> 1); pv->maxy = (int8_t)(W.hi2y >> 1);
     pv->dimx = (uint8_t)W.dimx; pv->dimy = (uint8_t)W.dimy;
     pv->flags = W.flags;
     gs->npieces = (uint8_t)W.np;
@@ -1184,10 +1258,7 @@ DEV void env_reset_pre(const Ctx &e) {
 // ... and after it, on the owner lane: players, shop, masks, neighbourhood caches
 DEV bool env_reset_post(const Ctx &e, bool gen_ok) {
   EnvPriv *pv = e.pv;
-  if (!gen_ok) {
-    pv->flags |= F_MAPGEN_FAIL;
-    return false;
-  }
+  if (!gen_ok) return false;                               // (coop_generate has flagged why)
   for (int i = 0; i < pv->n_players; i++) player_reset(e, i);
   add_players(e);
   for (int k = 0; k < COG_N_SHOP; k++) e.sh[SH_SHOP + k] = COG_CARDS_PER_TYPE;

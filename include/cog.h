@@ -54,11 +54,20 @@ extern "C" {
 
 /* hazard flags reported per env by cog_env_hazards: reference UB or toolchain-dependent
  * behaviour that this engine defines */
+/* generation gave up: after the reference's bounded attempts, or at a placement this engine cannot
+ * hold where the reference, unbounded, would go on (a hex more than 62 cells from the origin, a 97th
+ * piece, more than 1,008 hexes placed after a piece left the hex lattice; every generation seen past
+ * one of these ends without a map in the reference too).  Raised as COG_ERR_MAPGEN "Failed to generate map". */
 #define COG_HAZ_MAPGEN_FAIL 0x01u
 #define COG_HAZ_ERASE_PAST 0x02u   /* map.cpp:727 erase past the end: GCC>=13 semantics used */
 #define COG_HAZ_Q9_OOB 0x04u       /* map.cpp:347-352 write past player_locations: dropped */
 #define COG_HAZ_Q24_CLAMP 0x08u    /* player.cpp:92 discard more than active: clamped */
 #define COG_HAZ_GRID_OVER 0x10u    /* map wider than the 48x48 observation: rejected */
+/* (GRID_OVER is the finished map's check alone, as the reference's finalize would overflow there; the
+ * reset or the sync of the launch that meets it raises COG_ERR_MAPGEN "larger than the 48x48
+ * observation grid".  Every other env of the batch holds its result; the flagged env's records and
+ * state are unspecified until its next reset, which generates again whatever flags it carries; its
+ * Info record, which a reset leaves alone, until its next episode end.) */
 #define COG_HAZ_OOB_LOOKUP 0x20u   /* hex lookup outside the map: reads as mountain */
 #define COG_HAZ_SCAN_OVER 0x40u    /* card scan past the DeckObs record */
 #define COG_HAZ_B_START_LT4 0x80u  /* start piece B with < 4 players */

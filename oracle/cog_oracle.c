@@ -123,6 +123,9 @@ typedef struct {
   uint8_t *arr;                /* hex_array (dimx x dimy codes) */
   pt loc[4];
   int loc_size;
+  /* counters of the last generation (orc_gen_stats); they decide nothing */
+  int gs_total, gs_placed, gs_depth, gs_offlat;
+  float gs_cmin, gs_cmax;
 } omap;
 
 /* ------------------------------------------------------------------------------------ */
@@ -214,6 +217,14 @@ static void add_piece(omap *m, int id, pt at, int rotation) {   /* map.cpp:309-3
   m->pieces = (int *)grow(m->pieces, &cp, m->npieces + 1, sizeof(int));
   m->cap_pieces = cp;
   m->pieces[m->npieces++] = id;
+  if (m->npieces > m->gs_placed) m->gs_placed = m->npieces;
+  for (int k = 0; k < p->n; k++) {
+    float lo = p->xy[k].x < p->xy[k].y ? p->xy[k].x : p->xy[k].y;
+    float hi = p->xy[k].x > p->xy[k].y ? p->xy[k].x : p->xy[k].y;
+    if (lo < m->gs_cmin) m->gs_cmin = lo;
+    if (hi > m->gs_cmax) m->gs_cmax = hi;
+    if (p->xy[k].x != floorf(p->xy[k].x) || p->xy[k].y != floorf(p->xy[k].y)) m->gs_offlat++;
+  }
   int need = m->nhex + p->n, ch = m->cap_hex;
   m->xy = (pt *)grow(m->xy, &ch, need, sizeof(pt));
   ch = m->cap_hex;
@@ -339,6 +350,7 @@ static int add_random_piece(omap *m, int id, uint32_t *rng) {   /* map.cpp:277-3
       cand[ncand++] = c;
     }
   }
+  if (ncand > m->gs_total) m->gs_total = ncand;
   int nvalid = 0;
   conn_t *valid = (conn_t *)malloc(sizeof(conn_t) * (size_t)(ncand + 1));
   pt fp[37];
@@ -392,6 +404,7 @@ static void erase_gcc13(uint64_t *v, int *n, uint64_t pos, uint32_t *flags) {
 static int generate(oenv *e, int failures, uint32_t rng) {  /* map.cpp:697-742; rng by value */
   if (failures >= COG_MAX_FAILURES) { e->flags |= ORC_F_MAPGEN_FAIL; return -1; }
   omap *m = &e->m;
+  if (failures > m->gs_depth) m->gs_depth = failures;
   uint64_t s = uid(&rng, 0, 1);
   pt origin = {0, 0};
   add_piece(m, COG_PIECE_START0 + (int)s, origin, 0);
@@ -660,6 +673,8 @@ static int env_reset(oenv *e) {                            /* environment.cpp:42
   e->agent = 0;
   e->obs->shared.phase = COG_PHASE_INACTIVE;
   map_reset(&e->m);
+  e->m.gs_total = e->m.gs_placed = e->m.gs_depth = e->m.gs_offlat = 0;
+  e->m.gs_cmin = e->m.gs_cmax = 0;
   if (generate(e, 0, e->rng)) return -1;
   for (int i = 0; i < e->n_players; i++) player_reset(e, i);
   add_players(e);
@@ -958,6 +973,28 @@ int orc_debug_state(const orc_vec *v, size_t i, uint32_t *out, size_t n_out) {
   tmp[k++] = (uint32_t)e->m.dimx | (uint32_t)e->m.dimy << 16;
   for (size_t j = 0; j < k && j < n_out; j++) out[j] = tmp[j];
   return (int)k;
+}
+
+int orc_gen_stats(const orc_vec *v, size_t i, int32_t *out, size_t n_out) {
+  const omap *m = &v->env[i].m;
+  int32_t tmp[ORC_GEN_STATS];
+  tmp[0] = m->gs_total; tmp[1] = m->gs_placed; tmp[2] = m->gs_depth;
+  tmp[3] = (int32_t)lrintf(floorf(m->gs_cmin)); tmp[4] = (int32_t)lrintf(ceilf(m->gs_cmax));
+  tmp[5] = (int32_t)m->dimx; tmp[6] = (int32_t)m->dimy;
+  /* the cells of the start piece (add_players: pieces[0], the first hexes of the list) */
+  int32_t x0 = 0, x1 = -1, y0 = 0, y1 = -1;
+  if (m->npieces > 0 && m->nhex >= PMETA[m->pieces[0]].n_hex) {
+    x0 = y0 = INT32_MAX; x1 = y1 = INT32_MIN;
+    for (int k = 0; k < PMETA[m->pieces[0]].n_hex; k++) {
+      const int32_t ix = m->hidx[2 * k], iy = m->hidx[2 * k + 1];
+      x0 = ix < x0 ? ix : x0; x1 = ix > x1 ? ix : x1;
+      y0 = iy < y0 ? iy : y0; y1 = iy > y1 ? iy : y1;
+    }
+  }
+  tmp[7] = x0; tmp[8] = x1; tmp[9] = y0; tmp[10] = y1;
+  tmp[11] = m->gs_offlat;
+  for (size_t j = 0; j < ORC_GEN_STATS && j < n_out; j++) out[j] = tmp[j];
+  return ORC_GEN_STATS;
 }
 
 /* ------------------------------------------------------------------------------------ */

@@ -57,6 +57,15 @@ uint32_t orc_flags(const orc_vec *v, size_t i);   /* per-env sticky hazard flags
 void orc_clear_flags(orc_vec *v);
 /* private state for debugging: 16 bytes per player + env scalars */
 int orc_debug_state(const orc_vec *v, size_t i, uint32_t *out, size_t n_out);
+/* counters of env i's last map generation (they decide nothing; a failed generation leaves what it
+ * reached): [0] the largest candidate total add_random_piece enumerated, [1] the largest number of
+ * placed pieces, [2] the recursion depth reached, [3] [4] the smallest and largest hex coordinate
+ * (x or y) ever placed, [5] [6] the final dimx, dimy, [7..10] the start piece's cells in the final
+ * hex_array: ix min, ix max, iy min, iy max, [11] hexes placed at a non-integer coordinate (a piece
+ * connected to a travel piece whose failed placement left it reset at the origin: half a cell off
+ * the lattice of the map).  Returns ORC_GEN_STATS. */
+#define ORC_GEN_STATS 12
+int orc_gen_stats(const orc_vec *v, size_t i, int32_t *out, size_t n_out);
 
 orc_sampler *orc_sampler_create(size_t n, uint32_t seed);
 orc_sampler *orc_sampler_create_at(size_t n, uint32_t seed, uint64_t first);   /* seeds seed + first + i */

@@ -17,6 +17,7 @@ env i of a batch == a 1-env batch seeded seed+i, sampler seeded sseed+i).
     python oracle/gen_golden.py              # writes tests/golden/*.npz and *.json
     python oracle/gen_golden.py --workloads  # ref_workloads.{npz,json} only
     python oracle/gen_golden.py --lategame   # ref_lategame.json + ref_lategame_digests.npz only
+    python oracle/gen_golden.py --bigmaps    # ref_maps_big.json only
 """
 from __future__ import annotations
 
@@ -286,9 +287,73 @@ def lategame():
     print(f"lategame: {len(kept)} seeds, specials {totals}")
 
 
+# Big maps, pinned by the reference: reset-only digests at 2, 4, 6 and 7 map pieces (ref_maps.json
+# stops at 5), with 2 and 3 players too (A starts only: a B start overflows player_locations).
+# Each group (difficulty, pieces, players) takes its seeds from the first 256-aligned window in
+# which the oracle raises no error flag, so that a test can reset the whole window as one batch;
+# from 6 pieces on most seeds erase past the end of valid_indices and cannot run here.
+# off_lattice: (difficulty, pieces, seed) of maps on which a failed travel placement leaves a small
+# piece reset at the origin and the recursion connects pieces to it there, half a cell off the map's
+# lattice (the oracle's gen_stats count such hexes); found among seeds 700000 + i and 1100000 + i,
+# i < 65536, the four of them that the reference built here can run.
+BIGMAPS = dict(pieces=(2, 4, 6, 7), difficulties=(1, 2), window=256, windows_tried=16,
+               keep={4: 24, 3: 8, 2: 8},
+               off_lattice=((2, 4, 713086), (2, 4, 762327), (2, 4, 1124763), (2, 4, 1163566)))
+
+
+def bigmaps():
+    cfg, out = BIGMAPS, []
+    err = po.F_MAPGEN_FAIL | po.F_GRID_OVER
+    zero = np.zeros(1, dtype=po.ACTION)
+    for diff in cfg["difficulties"]:
+        for npc in cfg["pieces"]:
+            for np_ in (4, 3, 2):
+                for w in range(cfg["windows_tried"]):
+                    lo = w * cfg["window"]
+                    o = po.OracleVec(cfg["window"])
+                    try:
+                        o.reset_threaded(lo, np_, npc, diff, 100000)
+                    except RuntimeError:
+                        continue
+                    flags = o.flags()
+                    if not (flags & err).any():
+                        break
+                else:
+                    raise SystemExit(f"no clean window: diff={diff} npc={npc} players={np_}")
+                safe = [lo + int(i) for i in np.nonzero((flags & po.REF_UNSAFE) == 0)[0]][:cfg["keep"][np_]]
+                for s in safe:
+                    r, o1 = po.RefVec1(), po.OracleVec(1)
+                    r.reset(s, np_, npc, diff, 100000)
+                    o1.reset(s, np_, npc, diff, 100000)
+                    d = digest_env(r, zero)
+                    if d != digest_env(o1, zero):
+                        raise SystemExit(f"map mismatch seed={s} diff={diff} npc={npc} players={np_}")
+                    out.append((diff, npc, s, d.hex(), np_))
+                print(f"bigmaps: diff {diff}, {npc} pieces, {np_} players: {len(safe)} reference maps from window {lo}")
+    off = []
+    for diff, npc, s in cfg["off_lattice"]:
+        r, o1 = po.RefVec1(), po.OracleVec(1)
+        o1.reset(s, 4, npc, diff, 100000)
+        assert not o1.flags(0) & po.REF_UNSAFE and o1.gen_stats()["offlat"][0] > 0, s
+        r.reset(s, 4, npc, diff, 100000)
+        d = digest_env(r, zero)
+        if d != digest_env(o1, zero):
+            raise SystemExit(f"off-lattice map mismatch seed={s} diff={diff} npc={npc}")
+        off.append((diff, npc, s, d.hex(), 4))
+    with open(os.path.join(OUT, "ref_maps_big.json"), "w") as f:
+        json.dump(dict(source="oracle/_ref (unmodified reference core) via oracle/gen_golden.py --bigmaps",
+                       entry="[difficulty, n_pieces, seed, digest, n_players]: sha256[:8] over named leaves of obs, "
+                             "sel, rewards, dones, agent_sel, infos and one all-zero action record, after reset",
+                       window=cfg["window"], entries=out, off_lattice=off), f)
+    print(f"bigmaps: {len(out)} reference maps, {len(off)} off-lattice ones")
+
+
 def main():
     assert po.ref_available(), "build the reference first: make -C oracle ref"
     os.makedirs(OUT, exist_ok=True)
+    if "--bigmaps" in sys.argv:
+        bigmaps()
+        return
     if "--workloads" in sys.argv:
         workloads()
         return

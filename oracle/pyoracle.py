@@ -44,6 +44,8 @@ F_MAPGEN_FAIL, F_ERASE_PAST, F_Q9_OOB, F_Q24_CLAMP = 0x01, 0x02, 0x04, 0x08
 F_GRID_OVER, F_OOB_LOOKUP, F_SCAN_OVER, F_B_START_LT4 = 0x10, 0x20, 0x40, 0x80
 # seeds with any of these cannot be run by the reference built against libstdc++ 11
 REF_UNSAFE = F_ERASE_PAST | F_Q9_OOB | F_GRID_OVER | F_OOB_LOOKUP | F_SCAN_OVER | F_B_START_LT4 | F_Q24_CLAMP
+# orc_gen_stats, in its order (cog_oracle.h)
+GEN_STATS = ("total", "placed", "depth", "cmin", "cmax", "dimx", "dimy", "sx0", "sx1", "sy0", "sy1", "offlat")
 
 
 def leaves(a, prefix=""):
@@ -127,6 +129,7 @@ class _Lib:
             lib.orc_flags.argtypes = [vp, sz]
             lib.orc_clear_flags.argtypes = [vp]
             lib.orc_debug_state.argtypes = [vp, sz, C.POINTER(C.c_uint32), sz]
+            lib.orc_gen_stats.argtypes = [vp, sz, C.POINTER(C.c_int32), sz]
             lib.orc_sampler_create.restype = vp
             lib.orc_sampler_create.argtypes = [sz, C.c_uint32]
             lib.orc_sampler_create_at.restype = vp
@@ -222,6 +225,41 @@ class OracleVec:
         out = (C.c_uint32 * 64)()
         k = self.lib.orc_debug_state(self.h, i, out, 64)
         return list(out[:k])
+
+    def gen_stats(self, envs=None):
+        """Counters of every env's (or of `envs`') last map generation, one int32 array per name
+        (GEN_STATS): they decide nothing, a failed generation leaves what it reached."""
+        if envs is not None:
+            row = (C.c_int32 * len(GEN_STATS))()
+            out = np.zeros((len(envs), len(GEN_STATS)), dtype=np.int32)
+            for k, i in enumerate(envs):
+                self.lib.orc_gen_stats(self.h, int(i), row, len(GEN_STATS))
+                out[k] = row[:]
+            return {nm: out[:, j] for j, nm in enumerate(GEN_STATS)}
+        out = np.zeros((self.n, len(GEN_STATS)), dtype=np.int32)
+        row = (C.c_int32 * len(GEN_STATS))()
+        for i in range(self.n):
+            k = self.lib.orc_gen_stats(self.h, i, row, len(GEN_STATS))
+            assert k == len(GEN_STATS)
+            out[i] = row[:]
+        return {nm: out[:, j] for j, nm in enumerate(GEN_STATS)}
+
+    def player_cells(self):
+        """int[n, 4, 2]: the hex_array cell (ix, iy) of every player's location (map.cpp:273-275:
+        (size_t)(loc - min) + 1), and int[n, 2]: dimx, dimy."""
+        cells = np.zeros((self.n, 4, 2), dtype=np.int64)
+        dims = np.zeros((self.n, 2), dtype=np.int64)
+
+        def s16(v):
+            return v - 0x10000 if v & 0x8000 else v
+        for i in range(self.n):
+            d = self.debug_state(i)
+            mnx, mny = s16(d[26] & 0xffff), s16(d[26] >> 16)
+            dims[i] = d[27] & 0xffff, d[27] >> 16
+            for p in range(4):
+                w = d[6 + 5 * p + 4]
+                cells[i, p] = (s16(w & 0xffff) - mnx) // 2 + 1, (s16(w >> 16) - mny) // 2 + 1
+        return cells, dims
 
     def __del__(self):
         try:
