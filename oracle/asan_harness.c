@@ -9,6 +9,11 @@
  *   make -C oracle asan      -> oracle/_asan/harness_asan (sanitized) and oracle/_asan/harness (plain)
  *   oracle/_asan/harness_asan              one line per scenario: name, steps, resets, FNV-1a hash, flags
  *   oracle/_asan/harness_asan --selftest   a deliberate heap overread (the sanitizer must stop it)
+ *   oracle/_asan/harness_asan --drivers    the scenarios of kDriverScen instead (tests/test_driver_sequences_cpu.py):
+ *                                          auto-reset off (orc_set_autoreset) past every env's end, then
+ *                                          reset_default and auto-reset on again; and host actions past
+ *                                          their heads, clamped to (21, 21, 21, 6, 18) as the engine
+ *                                          documents (COG_HAZ_BAD_ACTION), in a tenth of the slots
  *
  * Scenarios: the reference trace sets of tests/golden/ref_traces (oracle/gen_golden.py traces():
  * the stored-mask driver with auto-resets, B-start seeds, 2 and 3 players, the selected-mask
@@ -32,16 +37,24 @@ typedef struct {
   int stored; /* 1: the current agent's stored mask (test_environment.cpp:97-98); 0: selected masks */
   int steps;
   size_t n;
+  int no_reset; /* steps run with orc_set_autoreset(v, 0); then reset_default, the switch on, `steps` again */
+  int clamped;  /* 1: a tenth of the (env, head) slots hold the head's clamp value, legal or not */
 } scenario;
 
 static const scenario kScen[] = {
-    {"C2shape_sel_medium", 12345, 4, 3, 1, 100000, 12345, 0, 1000, 16},
-    {"C3shape_sel_hard", 12345, 4, 3, 2, 100000, 12345, 0, 1000, 16},
-    {"stored_hard_ms30", 7, 4, 3, 2, 30, 7, 1, 1500, 16},
-    {"stored_medium_ms40_bstart", 70000, 4, 3, 1, 40, 70000, 1, 1500, 16},
-    {"c1like_2p_medium_sel", 0, 2, 3, 1, 100000, 0, 0, 20000, 1},
-    {"c1like_2p_medium_sto", 0, 2, 3, 1, 100000, 0, 1, 5000, 1},
-    {"p3_hard_sto_ms60", 300, 3, 3, 2, 60, 300, 1, 1500, 8},
+    {"C2shape_sel_medium", 12345, 4, 3, 1, 100000, 12345, 0, 1000, 16, 0, 0},
+    {"C3shape_sel_hard", 12345, 4, 3, 2, 100000, 12345, 0, 1000, 16, 0, 0},
+    {"stored_hard_ms30", 7, 4, 3, 2, 30, 7, 1, 1500, 16, 0, 0},
+    {"stored_medium_ms40_bstart", 70000, 4, 3, 1, 40, 70000, 1, 1500, 16, 0, 0},
+    {"c1like_2p_medium_sel", 0, 2, 3, 1, 100000, 0, 0, 20000, 1, 0, 0},
+    {"c1like_2p_medium_sto", 0, 2, 3, 1, 100000, 0, 1, 5000, 1, 0, 0},
+    {"p3_hard_sto_ms60", 300, 3, 3, 2, 60, 300, 1, 1500, 8, 0, 0},
+};
+static const scenario kDriverScen[] = {
+    {"stored_hard_ms8_noreset", 77, 4, 3, 2, 8, 77, 1, 120, 16, 1, 0},
+    {"sel_hard_ms8_noreset_3p", 77, 3, 3, 2, 8, 77, 0, 120, 16, 1, 0},
+    {"clamped_host_actions_sel", 77, 4, 3, 2, 8, 77, 0, 300, 16, 0, 1},
+    {"clamped_host_actions_sto", 78, 2, 3, 1, 12, 78, 1, 300, 16, 0, 1},
 };
 
 static uint64_t fnv(uint64_t h, const void *p, size_t b) {
@@ -59,8 +72,11 @@ int main(int argc, char **argv) {
     return v == 0x5a ? 3 : 4;
   }
   int bad = 0;
-  for (size_t q = 0; q < sizeof(kScen) / sizeof(kScen[0]); q++) {
-    const scenario *sc = &kScen[q];
+  const int drivers = argc > 1 && !strcmp(argv[1], "--drivers");
+  const scenario *list = drivers ? kDriverScen : kScen;
+  const size_t n_list = drivers ? sizeof(kDriverScen) / sizeof(kDriverScen[0]) : sizeof(kScen) / sizeof(kScen[0]);
+  for (size_t q = 0; q < n_list; q++) {
+    const scenario *sc = &list[q];
     orc_vec *v = orc_create(sc->n);
     orc_sampler *s = orc_sampler_create(sc->n, sc->sampler_seed);
     uint8_t *masks = (uint8_t *)calloc(sc->n, COG_MASK_BYTES);
@@ -72,7 +88,14 @@ int main(int argc, char **argv) {
     }
     uint64_t h = 0xcbf29ce484222325ull;
     long resets = 0;
-    for (int t = 0; t < sc->steps; t++) {
+    uint32_t lcg = sc->seed * 2654435761u + 1u;
+    const int total = sc->no_reset ? 2 * sc->steps : sc->steps;
+    if (sc->no_reset) orc_set_autoreset(v, 0);
+    for (int t = 0; t < total; t++) {
+      if (sc->no_reset && t == sc->steps) {                /* every env restarts; the switch back on */
+        if (orc_reset_default(v)) bad = 1;
+        orc_set_autoreset(v, 1);
+      }
       const uint8_t *obs = (const uint8_t *)orc_obs(v);
       const uint8_t *agent = orc_agent_sel(v);
       if (sc->stored) {
@@ -83,6 +106,15 @@ int main(int argc, char **argv) {
         orc_sample(s, masks);
       } else {
         orc_sample(s, orc_sel(v));
+      }
+      if (sc->clamped) {
+        static const uint8_t top[5] = {21, 21, 21, 6, 18};
+        uint8_t *a = (uint8_t *)orc_sampler_actions(s);
+        for (size_t i = 0; i < sc->n; i++)
+          for (int k = 0; k < 5; k++) {
+            lcg = lcg * 1664525u + 1013904223u;
+            if ((lcg >> 16) % 10u == 0u) a[i * COG_ACTION_BYTES + (size_t)k] = top[k];
+          }
       }
       orc_step(v, orc_sampler_actions(s));
       h = fnv(h, orc_obs(v), sc->n * COG_OBS_BYTES);

@@ -166,6 +166,7 @@ struct orc_vec {
   uint8_t *agent_sel;
   cog_info_t *infos;
   oenv *env;
+  uint8_t autoreset;   /* orc_set_autoreset: 1 (default) vec_cog_env::step's reset of a finished env */
 };
 
 /* ---- map primitives ---------------------------------------------------------------- */
@@ -831,6 +832,7 @@ static void mask_default(cog_action_mask_t *m) {          /* ActionMask() ctor, 
 orc_vec *orc_create(size_t n) {
   orc_vec *v = (orc_vec *)calloc(1, sizeof(orc_vec));
   v->n = n;
+  v->autoreset = 1;
   v->obs = (cog_obs_t *)aligned_alloc(64, n * sizeof(cog_obs_t) + 64);
   v->sel = (cog_action_mask_t *)aligned_alloc(64, n * sizeof(cog_action_mask_t) + 64);
   v->infos = (cog_info_t *)aligned_alloc(64, n * sizeof(cog_info_t) + 64);
@@ -885,21 +887,30 @@ int orc_reset(orc_vec *v, uint32_t seed, uint8_t n_players, uint8_t n_pieces, in
 }
 
 /* orc_reset over n_threads threads (envs are independent; each env's reset is the serial one) */
-typedef struct { orc_vec *v; uint32_t seed; uint8_t np, npc; int diff; uint32_t ms; size_t lo, hi; int rc; } reset_arg;
+typedef struct { orc_vec *v; uint32_t seed; uint8_t np, npc; int diff; uint32_t ms; size_t lo, hi; int rc; int keep; } reset_arg;
 static void *reset_worker(void *p) {
   reset_arg *a = (reset_arg *)p;
   for (size_t i = a->lo; i < a->hi; i++) {
     oenv *e = &a->v->env[i];
-    e->n_players = a->np; e->n_pieces = a->npc; e->difficulty = (uint8_t)a->diff;
-    e->max_steps = a->ms;
-    e->seed = (uint32_t)(a->seed + (uint32_t)i);
-    e->rng = mr_seed(e->seed);
+    if (!a->keep) {                                          /* (keep: orc_reset_default's reset) */
+      e->n_players = a->np; e->n_pieces = a->npc; e->difficulty = (uint8_t)a->diff;
+      e->max_steps = a->ms;
+      e->seed = (uint32_t)(a->seed + (uint32_t)i);
+      e->rng = mr_seed(e->seed);
+    }
     if (env_reset(e)) a->rc = -1;
   }
   return NULL;
 }
+static int reset_threads(orc_vec *v, uint32_t seed, uint8_t n_players, uint8_t n_pieces, int difficulty,
+                         uint32_t max_steps, int n_threads, int keep);
 int orc_reset_threaded(orc_vec *v, uint32_t seed, uint8_t n_players, uint8_t n_pieces, int difficulty,
                        uint32_t max_steps, int n_threads) {
+  return reset_threads(v, seed, n_players, n_pieces, difficulty, max_steps, n_threads, 0);
+}
+int orc_reset_default_threaded(orc_vec *v, int n_threads) { return reset_threads(v, 0, 0, 0, 0, 0, n_threads, 1); }
+static int reset_threads(orc_vec *v, uint32_t seed, uint8_t n_players, uint8_t n_pieces, int difficulty,
+                         uint32_t max_steps, int n_threads, int keep) {
   if (n_threads < 1) n_threads = 1;
   pthread_t *th = (pthread_t *)calloc((size_t)n_threads, sizeof(pthread_t));
   reset_arg *ra = (reset_arg *)calloc((size_t)n_threads, sizeof(reset_arg));
@@ -907,7 +918,7 @@ int orc_reset_threaded(orc_vec *v, uint32_t seed, uint8_t n_players, uint8_t n_p
   int rc = 0;
   for (int i = 0; i < n_threads; i++) {
     ra[i] = (reset_arg){v, seed, n_players, n_pieces, difficulty, max_steps, (size_t)i * b,
-                        i < n_threads - 1 ? (size_t)(i + 1) * b : v->n, 0};
+                        i < n_threads - 1 ? (size_t)(i + 1) * b : v->n, 0, keep};
     pthread_create(&th[i], NULL, reset_worker, &ra[i]);
   }
   for (int i = 0; i < n_threads; i++) {
@@ -931,11 +942,15 @@ int orc_step_range(orc_vec *v, const void *actions, size_t lo, size_t hi) {
     oenv *e = &v->env[i];
     env_step(e, &a[i]);
     v->dones[i] = e->done;
-    if (e->done && env_reset(e)) rc = -1;
+    if (e->done && v->autoreset && env_reset(e)) rc = -1;
     v->agent_sel[i] = e->agent;
   }
   return rc;
 }
+/* off: cog_env::step alone (environment.cpp:91-95) without the vec wrapper's reset
+   (vec_environment.h:56-59): a finished env stays done, env_step returns at once on it, and its
+   records stand until orc_reset / orc_reset_default */
+void orc_set_autoreset(orc_vec *v, int on) { v->autoreset = on ? 1 : 0; }
 int orc_step(orc_vec *v, const void *actions) { return orc_step_range(v, actions, 0, v->n); }
 
 void *orc_obs(orc_vec *v) { return v->obs; }
@@ -1045,13 +1060,28 @@ void orc_sample_range(orc_sampler *s, const void *masks, size_t lo, size_t hi) {
   }
 }
 void orc_sample(orc_sampler *s, const void *masks) { orc_sample_range(s, masks, 0, s->n); }
+/* the full-dynamics driver's masks (test_environment.cpp:97-98): env i's current agent's stored
+   mask; the env's own agent, which after a reset is 0 while agent_selections still holds the last
+   step's (vec_environment.h:32-44 leaves that view alone) */
+void orc_sample_stored_range(orc_sampler *s, const orc_vec *v, size_t lo, size_t hi) {
+  for (size_t i = lo; i < hi; i++) {
+    const cog_action_mask_t *m = &v->obs[i].player_data[v->env[i].agent].action_mask;
+    cog_action_t *a = &s->actions[i];
+    uint32_t *r = &s->rng[i];
+    a->play = sample_head(r, m->play, 22);
+    a->play_special = sample_head(r, m->play_special, 22);
+    a->remove = sample_head(r, m->remove, 22);
+    a->move = sample_head(r, m->move, 7);
+    a->get_from_shop = sample_head(r, m->get_from_shop, 19);
+  }
+}
 void *orc_sampler_actions(orc_sampler *s) { return s->actions; }
 
 /* ------------------------------------------------------------------------------------ */
 /* threaded CPU baseline in the shape of ThreadedRunner (runner.h:21-64)                  */
 /* ------------------------------------------------------------------------------------ */
 typedef struct {
-  orc_vec *v; orc_sampler *s; size_t lo, hi; int steps; int cpu;
+  orc_vec *v; orc_sampler *s; size_t lo, hi; int steps; int cpu; int stored;
   pthread_barrier_t *bar;
 } worker_arg;
 
@@ -1063,7 +1093,8 @@ static void *worker(void *p) {
   }
   pthread_barrier_wait(w->bar);
   for (int t = 0; t < w->steps; t++) {
-    orc_sample_range(w->s, w->v->sel, w->lo, w->hi);        /* runner.h:46-50 */
+    if (w->stored) orc_sample_stored_range(w->s, w->v, w->lo, w->hi);
+    else orc_sample_range(w->s, w->v->sel, w->lo, w->hi);   /* runner.h:46-50 */
     orc_step_range(w->v, w->s->actions, w->lo, w->hi);      /* runner.h:51-55 */
     pthread_barrier_wait(w->bar);                           /* step_sync per step */
   }
@@ -1071,6 +1102,9 @@ static void *worker(void *p) {
 }
 
 double orc_run_threaded(orc_vec *v, orc_sampler *s, int steps, int n_threads) {
+  return orc_run_threaded_masks(v, s, steps, n_threads, 0);
+}
+double orc_run_threaded_masks(orc_vec *v, orc_sampler *s, int steps, int n_threads, int stored) {
   if (n_threads < 1) n_threads = 1;
   cpu_set_t allowed; CPU_ZERO(&allowed);
   sched_getaffinity(0, sizeof(allowed), &allowed);
@@ -1082,7 +1116,7 @@ double orc_run_threaded(orc_vec *v, orc_sampler *s, int steps, int n_threads) {
   worker_arg *wa = (worker_arg *)calloc((size_t)n_threads, sizeof(worker_arg));
   size_t batch = v->n / (size_t)n_threads;
   for (int i = 0; i < n_threads; i++) {
-    wa[i].v = v; wa[i].s = s; wa[i].steps = steps; wa[i].bar = &bar;
+    wa[i].v = v; wa[i].s = s; wa[i].steps = steps; wa[i].bar = &bar; wa[i].stored = stored;
     wa[i].lo = (size_t)i * batch;
     wa[i].hi = i < n_threads - 1 ? wa[i].lo + batch : v->n;
     wa[i].cpu = ncpu > 0 ? cpus[(i + 1) % ncpu] : -1;   /* leave cpus[0] to the main thread */

@@ -43,10 +43,15 @@ int orc_reset(orc_vec *v, uint32_t seed, uint8_t n_players, uint8_t n_pieces,
 int orc_reset_default(orc_vec *v);
 int orc_reset_threaded(orc_vec *v, uint32_t seed, uint8_t n_players, uint8_t n_pieces,
                        int difficulty, uint32_t max_steps, int n_threads);
+int orc_reset_default_threaded(orc_vec *v, int n_threads);   /* orc_reset_default over host threads */
 /* vec_cog_env::step: actions = n ActionData records (64 B stride) */
 int orc_step(orc_vec *v, const void *actions);
 /* step only envs [lo, hi) */
 int orc_step_range(orc_vec *v, const void *actions, size_t lo, size_t hi);
+/* on (default): a finished env is reset inside the same step call (vec_environment.h:56-59).
+ * off: cog_env::step alone (environment.cpp:91-95): the env stays done, later steps change nothing
+ * of it, its records stand until orc_reset / orc_reset_default */
+void orc_set_autoreset(orc_vec *v, int on);
 void *orc_obs(orc_vec *v);            /* ObsData[n] */
 void *orc_sel(orc_vec *v);            /* ActionMask[n] */
 float *orc_rewards(orc_vec *v);       /* f32[n][4] */
@@ -72,12 +77,17 @@ orc_sampler *orc_sampler_create_at(size_t n, uint32_t seed, uint64_t first);   /
 void orc_sampler_destroy(orc_sampler *s);
 void orc_sample(orc_sampler *s, const void *masks);   /* ActionMask[n] -> actions */
 void orc_sample_range(orc_sampler *s, const void *masks, size_t lo, size_t hi);
+/* the same from the stored mask of each env's current agent (the env's own, not the
+ * agent_selections view, which a reset leaves stale): the full-dynamics driver */
+void orc_sample_stored_range(orc_sampler *s, const orc_vec *v, size_t lo, size_t hi);
 void *orc_sampler_actions(orc_sampler *s);            /* ActionData[n] */
 
 /* reference ThreadedRunner shape (runner.h:21-64): contiguous env blocks, one pinned worker
  * per block, per step "sample(selected masks); step(actions)" then a barrier.
  * Returns wall seconds for `steps` steps. */
 double orc_run_threaded(orc_vec *v, orc_sampler *s, int steps, int n_threads);
+/* the same loop; stored != 0 samples each env's current agent's stored mask instead */
+double orc_run_threaded_masks(orc_vec *v, orc_sampler *s, int steps, int n_threads, int stored);
 
 #ifdef __cplusplus
 }

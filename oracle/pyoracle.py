@@ -120,8 +120,10 @@ class _Lib:
             lib.orc_reset.argtypes = [vp, C.c_uint32, C.c_uint8, C.c_uint8, C.c_int, C.c_uint32]
             lib.orc_reset_default.argtypes = [vp]
             lib.orc_reset_threaded.argtypes = [vp, C.c_uint32, C.c_uint8, C.c_uint8, C.c_int, C.c_uint32, C.c_int]
+            lib.orc_reset_default_threaded.argtypes = [vp, C.c_int]
             lib.orc_step.argtypes = [vp, vp]
             lib.orc_step_range.argtypes = [vp, vp, sz, sz]
+            lib.orc_set_autoreset.argtypes = [vp, C.c_int]
             for f in ("orc_obs", "orc_sel", "orc_rewards", "orc_dones", "orc_agent_sel", "orc_infos"):
                 getattr(lib, f).restype = vp
                 getattr(lib, f).argtypes = [vp]
@@ -140,6 +142,9 @@ class _Lib:
             lib.orc_sampler_actions.argtypes = [vp]
             lib.orc_run_threaded.restype = C.c_double
             lib.orc_run_threaded.argtypes = [vp, vp, C.c_int, C.c_int]
+            lib.orc_run_threaded_masks.restype = C.c_double
+            lib.orc_run_threaded_masks.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
+            lib.orc_sample_stored_range.argtypes = [vp, vp, sz, sz]
             cls._oracle = lib
         return cls._oracle
 
@@ -204,14 +209,21 @@ class OracleVec:
                                        max_steps, threads):
             raise RuntimeError("Failed to generate map in specified maximum number of attempts")
 
-    def reset_default(self):
-        if self.lib.orc_reset_default(self.h):
+    def reset_default(self, threads=None):
+        """threads: split over that many host threads (bit-identical: envs are independent)."""
+        if (self.lib.orc_reset_default_threaded(self.h, threads) if threads and threads > 1 else
+                self.lib.orc_reset_default(self.h)):
             raise RuntimeError("Failed to generate map in specified maximum number of attempts")
 
     def step(self, actions):
         actions = np.ascontiguousarray(actions, dtype=ACTION)
         if self.lib.orc_step(self.h, actions.ctypes.data):
             raise RuntimeError("Failed to generate map in specified maximum number of attempts")
+
+    def set_autoreset(self, on):
+        """on (default): a finished env is reset inside the same step (vec_environment.h:56-59);
+        off: cog_env::step alone (environment.cpp:91-95): it stays done until reset()."""
+        self.lib.orc_set_autoreset(self.h, 1 if on else 0)
 
     def flags(self, i=None):
         if i is None:
@@ -284,6 +296,11 @@ class OracleSampler:
         masks = np.ascontiguousarray(masks, dtype=MASK)
         self.lib.orc_sample(self.h, masks.ctypes.data)
 
+    def sample_stored(self, vec):
+        """sample() from the stored mask of every env's own current agent, as the stored-mask
+        kernels do (after a reset that is agent 0, whatever the agent_selection view still shows)."""
+        self.lib.orc_sample_stored_range(self.h, vec.h, 0, self.n)
+
     def __del__(self):
         try:
             self.lib.orc_sampler_destroy(self.h)
@@ -312,7 +329,9 @@ def host_threads():
     return max(1, min(allowed, share))
 
 
-def run_threaded(vec: OracleVec, sampler: OracleSampler, steps: int, n_threads: int) -> float:
+def run_threaded(vec: OracleVec, sampler: OracleSampler, steps: int, n_threads: int, stored: bool = False) -> float:
+    if stored:
+        return _Lib.oracle().orc_run_threaded_masks(vec.h, sampler.h, steps, n_threads, 1)
     return _Lib.oracle().orc_run_threaded(vec.h, sampler.h, steps, n_threads)
 
 
