@@ -747,6 +747,13 @@ int cog_abi_version(void) { return COG_ABI_VERSION; }
 int cog_rollout_kind(size_t n_envs, int n_players, int stored_masks) {
   return cog::rollout_kind_of(n_envs, stored_masks ? cog::MASK_STORED : cog::MASK_SELECTED, n_players >= 3);
 }
+int cog_trio_form_of(size_t n_envs, int device, cog_trio_form *out) {
+  if (!out) return fail(COG_ERR_INVALID, "out is NULL");
+  if (device < 0 || device >= 64) return fail(COG_ERR_INVALID, "device out of range");
+  const cog::TrioForm f = cog::trio_form_of(n_envs, device);
+  *out = cog_trio_form{f.epw, f.workgroups, f.lat, f.wpc, f.pad_lds, f.fixup_grid, f.cus};
+  return COG_OK;
+}
 
 int cog_device_count(int *out) {
   if (!out) return fail(COG_ERR_INVALID, "out is NULL");

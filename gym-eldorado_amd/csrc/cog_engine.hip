@@ -3864,11 +3864,10 @@ struct CuShape {
   unsigned cus;
   size_t lds;
 };
-static CuShape cu_shape() {
+static CuShape cu_shape_of(int d) {
   static CuShape cache[64] = {};
   static std::once_flag filled[64];                        // (host threads may launch concurrently)
-  int d = 0;
-  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return {256u, 163840};
+  if (d < 0 || d >= 64) return {256u, 163840};
   std::call_once(filled[d], [d] {
     hipDeviceProp_t p;
     if (hipGetDeviceProperties(&p, d) == hipSuccess && p.multiProcessorCount > 0)
@@ -3879,20 +3878,42 @@ static CuShape cu_shape() {
   });
   return cache[d];
 }
-static size_t trio_pad_lds(unsigned nblocks) {
+static CuShape cu_shape() {
+  int d = 0;
+  return cu_shape_of(hipGetDevice(&d) == hipSuccess ? d : -1);
+}
+// (*wpc: the workgroups per CU asked for, 0 where none is; the pad is 0 where TrioLds alone leaves no
+// room for one: three and four per CU)
+static size_t trio_pad_lds(unsigned nblocks, const CuShape &c, int *wpc) {
   static const int forced = [] {
     const char *e = getenv("COG_TRIO_WPC");
     return e && *e ? atoi(e) : 0;
   }();
-  const CuShape c = cu_shape();
-  const int wpc = forced >= 1 && forced <= 4 ? forced : (nblocks > c.cus ? 2 : 0);
-  if (!wpc || c.lds / (size_t)wpc <= sizeof(TrioLds) + 2048) return 0;
-  return c.lds / (size_t)wpc - 2048 - sizeof(TrioLds);     // (a margin for the allocation granule)
+  *wpc = forced >= 1 && forced <= 4 ? forced : (nblocks > c.cus ? 2 : 0);
+  if (!*wpc || c.lds / (size_t)*wpc <= sizeof(TrioLds) + 2048) return 0;
+  return c.lds / (size_t)*wpc - 2048 - sizeof(TrioLds);    // (a margin for the allocation granule)
 }
 // k_env_fixup's grid: at most one one-wave workgroup per CU strides over the parked list.  A wave
 // per CU keeps a launch with every workgroup parked (short episodes) running in parallel, and a
 // launch with none parked cheap.
-static unsigned fixup_grid(unsigned nblocks) { return std::max(1u, std::min(nblocks, cu_shape().cus)); }
+static unsigned fixup_grid(unsigned nblocks, const CuShape &c) { return std::max(1u, std::min(nblocks, c.cus)); }
+// The form of a duo / trio launch over n envs on a device of shape c: what launch_rollout launches
+// and what cog_trio_form_of reports
+static TrioForm trio_form(size_t n, bool trio, const CuShape &c) {
+  static const int jt_env = [] {                           // $COG_TRIO_JT = 0 / 1 overrides (A/B)
+    const char *e = getenv("COG_TRIO_JT");
+    return e && *e ? atoi(e) : -1;
+  }();
+  TrioForm f;
+  f.epw = trio ? trio_epw(n) : 64;
+  f.workgroups = blocks_for(n, f.epw);
+  f.lat = jt_env >= 0 ? (jt_env != 0) : (f.workgroups <= c.cus ? 1 : 0);
+  f.pad_lds = trio_pad_lds(f.workgroups, c, &f.wpc);
+  f.fixup_grid = fixup_grid(f.workgroups, c);
+  f.cus = c.cus;
+  return f;
+}
+TrioForm trio_form_of(size_t n, int device) { return trio_form(n, true, cu_shape_of(device)); }
 int launch_rollout(const DevState &s, int mask_source, int steps, uint32_t *d_rng, uint8_t *d_actions, void *stream,
                    bool defer_ok, uint32_t *park_seq, bool no_fixup) {
   if (!s.n || steps <= 0) return 0;
@@ -3918,14 +3939,10 @@ int launch_rollout(const DevState &s, int mask_source, int steps, uint32_t *d_rn
     sd.park_par = (*park_seq)++ & 1u;
     // (the redo hook parks every env: never without the fix-up)
     sd.no_fixup = no_fixup && kind == RK_TRIO && (redo_at < 0 || park_nofix.first >= 0) ? 1u : 0u;
-    const int epw = kind == RK_TRIO ? trio_epw(s.n) : 64;
-    const unsigned nb = blocks_for(s.n, epw);
-    const dim3 g(nb), gf(fixup_grid(nb));
-    static const int jt_env = [] {                         // $COG_TRIO_JT = 0 / 1 overrides (A/B)
-      const char *e = getenv("COG_TRIO_JT");
-      return e && *e ? atoi(e) : -1;
-    }();
-    sd.trio_jt = jt_env >= 0 ? (uint32_t)(jt_env != 0) : (nb <= cu_shape().cus ? 1u : 0u);
+    const TrioForm f = trio_form(s.n, kind == RK_TRIO, cu_shape());
+    const int epw = f.epw;
+    const dim3 g(f.workgroups), gf(f.fixup_grid);
+    sd.trio_jt = (uint32_t)f.lat;
     if (mask_source == MASK_STORED) {
       hipLaunchKernelGGL((k_env_rollout_duo<MASK_STORED>), g, dim3(128), 0, st, sd, steps, d_rng, d_actions);
       hipLaunchKernelGGL((k_env_fixup<MASK_STORED>), gf, dim3(64), 0, st, sd, steps, d_rng, d_actions, epw);
@@ -3934,10 +3951,10 @@ int launch_rollout(const DevState &s, int mask_source, int steps, uint32_t *d_rn
       // never-inlined call -- was slower: 20-step launch at 8,192 44.2 / 42.0 against 41.3 us,
       // profiles/r04t_trio_fused.txt)
       if (sd.trio_jt)
-        hipLaunchKernelGGL((k_env_rollout_trio<MASK_SELECTED, true>), g, dim3(256), trio_pad_lds(nb), st, sd, steps, epw,
+        hipLaunchKernelGGL((k_env_rollout_trio<MASK_SELECTED, true>), g, dim3(256), f.pad_lds, st, sd, steps, epw,
                            d_rng, d_actions);
       else
-        hipLaunchKernelGGL((k_env_rollout_trio<MASK_SELECTED, false>), g, dim3(256), trio_pad_lds(nb), st, sd, steps, epw,
+        hipLaunchKernelGGL((k_env_rollout_trio<MASK_SELECTED, false>), g, dim3(256), f.pad_lds, st, sd, steps, epw,
                            d_rng, d_actions);
       if (!sd.no_fixup)
         hipLaunchKernelGGL((k_env_fixup<MASK_SELECTED>), gf, dim3(64), 0, st, sd, steps, d_rng, d_actions, epw);

@@ -349,6 +349,23 @@ PYBIND11_MODULE(_city_of_gold, m) {
       },
       "n"_a, "n_players"_a = 4, "stored_masks"_a = false,
       "the persistent rollout kernel launched for a shard of n envs: duo | pipe | wave | trio");
+  m.def(
+      "trio_form",
+      [](size_t n, int device) {
+        cog_trio_form f;
+        check(cog_trio_form_of(n, device, &f));
+        py::dict d;
+        d["epw"] = f.epw;
+        d["workgroups"] = f.workgroups;
+        d["lat"] = f.lat;
+        d["wpc"] = f.wpc;
+        d["pad_lds"] = f.pad_lds;
+        d["fixup_grid"] = f.fixup_grid;
+        d["cus"] = f.cus;
+        return d;
+      },
+      "n"_a, "device"_a = 0,
+      "the form of the trio launch over a shard of n envs on `device` (cog.h cog_trio_form), as the launcher computes it");
   m.def("default_devices", []() { return default_devices(); },
         "the GPUs a handle created with device=None uses (COG_DEVICES, else COG_DEVICE, else LOCAL_RANK, else 0)");
   m.def(

@@ -109,6 +109,16 @@ COG_API int cog_device_count(int *out);
  * (k_env_rollout_pipe), 3 trio (k_env_rollout_trio + k_env_fixup); $COG_ROLLOUT / $COG_TRIO
  * force one (cog_engine.hip rollout_kind) */
 COG_API int cog_rollout_kind(size_t n_envs, int n_players, int stored_masks);
+/* the form of the trio launch (k_env_rollout_trio + k_env_fixup) over a shard of n_envs envs on
+ * `device`, as cog_runner_rollout will launch it (read-only; computed by the launcher's own
+ * helpers): envs per workgroup (64, or 32 under $COG_TRIO_EPW), workgroups = ceil(n_envs / epw),
+ * lat 1 for the form taken by a launch of at most one workgroup per CU ($COG_TRIO_JT forces it),
+ * wpc the workgroups per CU the dynamic LDS pad keeps (2 when workgroups > cus, $COG_TRIO_WPC =
+ * 1..4 forces it; 0 when no pad is applied) and pad_lds its bytes (0 also where a CU's LDS over wpc
+ * leaves no room beside the kernel's own: wpc 3 and 4), k_env_fixup's grid
+ * (min(workgroups, cus)), and the CUs `device` exposes (256 where it cannot be asked) */
+typedef struct cog_trio_form { int epw; unsigned workgroups; int lat; int wpc; size_t pad_lds; unsigned fixup_grid; unsigned cus; } cog_trio_form;
+COG_API int cog_trio_form_of(size_t n_envs, int device, cog_trio_form *out);
 
 /* ---- vectorized environment ------------------------------------------------------------ */
 /* vec_cog_env<N>() (vec_environment.h:23-30): N default-constructed envs on `device`;

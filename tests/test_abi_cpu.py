@@ -21,7 +21,7 @@ def declared_symbols():
 def test_header_declares_entry_points():
     syms = declared_symbols()
     for must in ("cog_env_create", "cog_env_reset", "cog_env_step", "cog_sampler_sample",
-                 "cog_runner_step", "cog_runner_sync", "cog_last_error"):
+                 "cog_runner_step", "cog_runner_sync", "cog_last_error", "cog_rollout_kind", "cog_trio_form_of"):
         assert must in syms
 
 
@@ -135,3 +135,37 @@ def test_rollout_kind_selection():
         assert kind(8192, p, stored) == DUO and kind(16384, p, stored) == DUO
         assert kind(24576, p, stored) == PIPE and kind(32768, p, stored) == PIPE
         assert kind(65536, p, stored) == WAVE
+
+
+class TrioForm(ctypes.Structure):                           # cog.h cog_trio_form
+    _fields_ = [("epw", ctypes.c_int), ("workgroups", ctypes.c_uint), ("lat", ctypes.c_int), ("wpc", ctypes.c_int),
+                ("pad_lds", ctypes.c_size_t), ("fixup_grid", ctypes.c_uint), ("cus", ctypes.c_uint)]
+
+
+def test_trio_form_query(cg):
+    """cog_trio_form_of (read-only, no device needed: 256 CUs and 160 KiB of LDS where the device
+    cannot be asked): the header declares the struct as mirrored here, the C entry point and the
+    Python face agree, and the default form follows from the CU count alone -- 64 envs per
+    workgroup, LAT while workgroups <= cus, the two-per-CU LDS pad above, the fix-up grid capped at
+    the CUs."""
+    src = open(os.path.join(ROOT, "include", "cog.h")).read()
+    m = re.search(r"typedef struct cog_trio_form \{([^}]*)\} cog_trio_form;", src)
+    assert m, "cog.h does not declare cog_trio_form"
+    names = [re.split(r"\s+", d.strip())[-1] for d in m.group(1).split(";") if d.strip()]
+    assert names == [f[0] for f in TrioForm._fields_]
+    if any(os.environ.get(k) for k in ("COG_TRIO_EPW", "COG_TRIO_JT", "COG_TRIO_WPC")):
+        pytest.skip("trio form forced by the environment")
+    lib = ctypes.CDLL(LIB)
+    lib.cog_trio_form_of.argtypes = [ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(TrioForm)]
+    assert lib.cog_trio_form_of(64, 0, None) != 0 and lib.cog_trio_form_of(64, -1, ctypes.byref(TrioForm())) != 0
+    for n in (1, 33, 64, 65, 200, 8192, 16384, 16385, 24576, 65536):
+        f = TrioForm()
+        assert lib.cog_trio_form_of(n, 0, ctypes.byref(f)) == 0
+        d = cg._city_of_gold.trio_form(n)
+        assert d == {k: getattr(f, k) for k, _ in TrioForm._fields_}, n
+        assert sorted(d) == sorted(k for k, _ in TrioForm._fields_)
+        nb = -(-n // 64)
+        assert (f.epw, f.workgroups, f.fixup_grid) == (64, nb, min(nb, f.cus)) and f.cus >= 1, (n, d)
+        assert f.lat == int(nb <= f.cus) and f.wpc == (0 if nb <= f.cus else 2) and (f.pad_lds > 0) == (nb > f.cus), (n, d)
+        if cg.device_count() == 0:
+            assert f.cus == 256

@@ -9,6 +9,9 @@
   decks with card types >= 8 after greedy steps, and for every random sequence ends, wide decks
   and trio launches entered with and without the compact deck image
   G's numpy argmax against tests/policy_ref.py's float64 reference on the same masks
+  the sequences of the launch-form rows (tests/launch_form_cases.py, tests/test_gpu_launch_forms.py):
+  episode ends in every op that is meant to hold one, wide decks, trio launches entered both ways,
+  the flags the 2-player tail raises, and the rows' own form checks against cog_trio_form_of
 """
 import os
 import subprocess
@@ -17,6 +20,7 @@ import numpy as np
 import pytest
 
 import driver_cases as dc
+import launch_form_cases as lf
 import policy_ref as pr
 import pyoracle as po
 
@@ -285,6 +289,67 @@ def test_bad_action_case_on_the_oracle():
     assert np.array_equal(over.any(1), rows) and 0.05 < over.mean() < 0.15
     for k, nm in enumerate(dc.HEAD_NAMES):
         assert np.array_equal(clamped[nm], np.where(over[:, k], dc.CLAMP[k], 0))
+
+
+# ---- the launch-form rows ---------------------------------------------------------------------------
+@pytest.mark.parametrize("n", lf.SIZES)
+def test_launch_form_rollout_sequence_keeps_its_cases(n):
+    """Measured on the oracle at n = 200 (33): ends in ops 1..6 30, 170, 166, 24, 159, 156 (3, 30, 28, 5,
+    24, 28), in 8..10 17, 177, 150 (1, 32, 22), in the two T20 ops after A0 22, 178 (3, 30), every env
+    done before X0; up to 64 (12) envs with a card type >= 8 at once; trio launches entered with
+    cdeck_ok 1 / 0: 28 / 8; no hazard flag.  Conditions, not equalities."""
+    h = dc.Harness(None, n, dc.PAIR_SEED)
+    for k, op in enumerate(lf.ROLLOUT_SEQ):
+        h.apply(op)
+        if k + 1 == lf.ROLLOUT_ALL_DONE_AT:
+            assert np.asarray(h.orc.dones).all(), "an env has not ended before X0"
+    assert lf.ROLLOUT_SEQ[lf.ROLLOUT_ALL_DONE_AT] == "X0"
+    for k in lf.ROLLOUT_END_OPS:
+        assert h.op_ends[k] >= 1, f"n {n}: op {k} {lf.ROLLOUT_SEQ[k]!r} holds no episode end: {h.op_ends}"
+    assert h.wide_max > 0 and h.trio_loaded > 0 and h.trio_clear > 0, (h.wide_max, h.trio_loaded, h.trio_clear)
+    assert not h.orc.flags().any(), "the rollout sequence raises a hazard flag on the oracle"
+    # the 2-player tail behind a forced pipe / wave: flags to compare per env, and ends
+    for op in lf.TWO_PLAYER_TAIL:
+        h.apply(op)
+    flags = h.orc.flags()
+    for f in (po.F_ERASE_PAST, po.F_Q9_OOB, po.F_OOB_LOOKUP, po.F_B_START_LT4):
+        assert (flags & f).any(), f"n {n}: flag {f:#x} is not raised"
+    assert h.op_ends[-1] >= 1 and h.op_ends[-2] >= 1, h.op_ends
+
+
+def test_launch_form_host_and_redo_sequences_keep_their_cases():
+    for n in (200, lf.HOST_TWO_SHARD_N):                     # (measured at 200: 28 to 180 ends per op)
+        h = oracle_run(lf.HOST_SEQ, n)
+        assert all(e >= 1 for e in h.op_ends[1:]), (n, h.op_ends)
+    h = oracle_run(lf.REDO_SEQ)                              # (30, 180, 194 ends at max_steps 8, then none)
+    assert all(e >= 1 for e in h.op_ends[1:4]) and h.trio_loaded > 0 and h.trio_clear > 0, h.op_ends
+
+
+def test_launch_form_rows_cover_the_forms():
+    """Every row's switches are among those the engine's sources read, the rows span both values of
+    every form figure, and check_form accepts what a device of 256 CUs gives and refuses a switch
+    that was ignored (cog_trio_form_of needs no device; this process has read no switch)."""
+    src = "".join(open(os.path.join(ROOT, "gym-eldorado_amd", "csrc", f)).read() for f in ("cog_engine.hip", "cog_abi.cpp"))
+    for r in lf.ROWS.values():
+        for k in r.env:
+            assert f'getenv("{k}")' in src, f"{r.name}: no source reads ${k}"
+        assert r.sizes and lf.sequence_of(r)[0][0] == "X"
+    assert {(r, n) for r, n in lf.CASES} >= {(r, n) for r in ("default", "no-lat", "epw32", "epw32-no-lat", "wpc1", "wpc2",
+                                                              "wpc3", "wpc4", "round3-duo", "pipe", "wave") for n in (200, 33)}
+    if any(os.environ.get(k) for k in lf.SWITCHES + ["COG_ROLLOUT", "COG_TRIO"]):
+        return                                               # (forms forced from outside: the rest does not apply)
+    from city_of_gold import _city_of_gold as C
+    for n in (200, 33, lf.BIG_N):
+        form = C.trio_form(n)
+        kinds = {f"{p},{int(s)}": C.rollout_kind(n, p, s) for p in (4, 3, 2) for s in (False, True)}
+        assert form["cus"] == 256 or C.device_count() > 0
+        if n != lf.BIG_N:
+            lf.check_form(lf.ROWS["default"], n, form, kinds)
+            for other in ("no-lat", "epw32", "wpc1", "wpc3", "round3-duo", "pipe"):
+                with pytest.raises(AssertionError):
+                    lf.check_form(lf.ROWS[other], n, form, kinds)
+        else:
+            assert form["workgroups"] == 257 and (form["cus"] != 256 or (form["lat"], form["wpc"], form["fixup_grid"]) == (0, 2, 256))
 
 
 # ---- G's mirror ------------------------------------------------------------------------------------
