@@ -824,6 +824,13 @@ int cog_env_shard_info(const cog_env *env, int k, size_t *first, size_t *count, 
   return COG_OK;
 }
 
+// What the trio rollout's lean step takes for granted of a batch (launch_rollout's defer_ok): a turn
+// passes to another player (>= 3 players), and an episode ends with a turn -- the lean step checks
+// the turn counter against max_steps at turn ends alone, which is the reference's check on every
+// step as long as max_steps >= 1.  At max_steps 0 every step ends its episode, the first after a
+// reset included, so such a batch takes the kernels of the full step, as one of 1 or 2 players does.
+static bool trio_ok(const cog_env *e) { return e->n_players >= 3 && e->max_steps != 0; }
+
 static int env_reset_impl(cog_env *e, const cog::ResetParams &p) {
   int rc = prepare_host(e);
   if (rc) return rc;
@@ -835,7 +842,7 @@ static int env_reset_impl(cog_env *e, const cog::ResetParams &p) {
   for (EnvShard &k : e->sh) {
     k.done.queued = false;
     k.host_synced = false;                                 // (refresh_full: the mirror is rebuilt later)
-    k.lean_clock = e->n_players >= 3 && e->max_steps ? 0ull : ~0ull;
+    k.lean_clock = trio_ok(e) ? 0ull : ~0ull;
     k.cdeck_ok = false;
   }
   for (EnvShard &k : e->sh) {
@@ -1689,7 +1696,8 @@ static int runner_launch_fused(cog_runner *r, int steps) {
     }
     const cog::DevState s = launch_state(k, host);
     if (r->chunk > 1) {                                    // persistent kernels, chunk steps each
-      const bool trio = cog::rollout_kind_of(k.n, src, r->env->n_players >= 3) == 3;
+      const bool defer_ok = trio_ok(r->env);
+      const bool trio = cog::rollout_kind_of(k.n, src, defer_ok) == 3;
       for (int t = 0; t < steps; t += r->chunk) {
         const int kk = std::min(r->chunk, steps - t);
         // no env can park in this launch (EnvShard::lean_clock): no fix-up launch
@@ -1697,7 +1705,7 @@ static int runner_launch_fused(cog_runner *r, int steps) {
                               k.lean_clock + (uint64_t)kk < (uint64_t)r->env->max_steps;
         cog::DevState sc = s;
         sc.cdeck_ok = trio && k.cdeck_ok ? 1u : 0u;
-        if (cog::launch_rollout(sc, src, kk, q.d_rng, q.d_actions, k.stream, r->env->n_players >= 3, &k.park_seq,
+        if (cog::launch_rollout(sc, src, kk, q.d_rng, q.d_actions, k.stream, defer_ok, &k.park_seq,
                                 no_fixup))
           return fail(COG_ERR_HIP, std::string("rollout launch failed: ") + hipGetErrorString(hipGetLastError()));
         k.lean_clock = trio && k.lean_clock != ~0ull ? k.lean_clock + (uint64_t)kk : ~0ull;

@@ -196,8 +196,9 @@ size_t publish_mirror_bytes(size_t n, size_t outs_bytes);
 bool publish_can_signal(size_t n, size_t outs_bytes, bool actions);
 int launch_sample_step(const DevState &s, int mask_source, uint32_t *d_rng, uint8_t *d_actions,
                        void *stream);
-// persistent K-step runner loop; defer_ok: every env of the shard has >= 3 players (the trio
-// rollout's deferred turn end then runs the selected-mask loop at every shard size)
+// persistent K-step runner loop; defer_ok: every env of the shard has >= 3 players and a max_steps
+// of 1 or more (the trio rollout's deferred turn end then runs the selected-mask loop at every shard
+// size; its lean step ends an episode at a turn end alone, cog_abi.cpp trio_ok)
 // park_seq: the shard's count of launches with a fix-up (counts them; alternate launches use
 // alternate counters of DevState::parkq)
 // no_fixup: the caller has shown that no env can park in this launch (cog_abi.cpp EnvShard::

@@ -455,7 +455,8 @@ DEV void trio_stepper(TrioLds &D, const DevState &s_glob, int steps, int epw, ui
       R.sh[0] = stepped ? (R.sh[0] & ~0xffu) | phase : R.sh[0];
       // done (environment.cpp:183-207): the (next) agent's cell or the turn counter.  Both change
       // only with the turn here (no move: the agent's cell is the one checked after its last step,
-      // never an end; a player's own cell is never an out-of-bounds lookup)
+      // never an end; a player's own cell is never an out-of-bounds lookup; max_steps >= 1, which
+      // the host guarantees -- at 0 the first step after a reset ends the episode, cog_abi.cpp trio_ok)
       finish = turn_end && (COG_HEX_END((own >> (8 * na)) & 0xffu) || R.turn_counter >= R.max_steps);
       R.g1x = finish ? (R.g1x & 0x00ffffffu) | (1u << 24) : R.g1x;   // R.set_done(1)
       PH(0);

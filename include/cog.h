@@ -107,7 +107,9 @@ COG_API int cog_device_count(int *out);
  * n_players players, sampling the selected (stored_masks 0) or stored masks (measurement labels
  * only): 0 duo (k_env_rollout_duo + k_env_fixup), 1 wave (k_env_rollout), 2 pipe
  * (k_env_rollout_pipe), 3 trio (k_env_rollout_trio + k_env_fixup); $COG_ROLLOUT / $COG_TRIO
- * force one (cog_engine.hip rollout_kind) */
+ * force one (cog_engine.hip rollout_kind).  One player selects like two (never the trio); a batch
+ * reset with max_steps 0 takes what two players take, whatever its players (the trio's step ends
+ * episodes at turn ends alone) */
 COG_API int cog_rollout_kind(size_t n_envs, int n_players, int stored_masks);
 /* the form of the trio launch (k_env_rollout_trio + k_env_fixup) over a shard of n_envs envs on
  * `device`, as cog_runner_rollout will launch it (read-only; computed by the launcher's own
@@ -135,7 +137,9 @@ COG_API int cog_env_shard_info(const cog_env *env, int shard, size_t *first, siz
 COG_API void cog_env_destroy(cog_env *env);
 COG_API int cog_env_num_envs(const cog_env *env, size_t *out);
 /* vec_cog_env::reset(seed, n_players, n_pieces, difficulty, max_steps, render)
- * (vec_environment.h:38-44): env i gets seed + i (u32).  Synchronous. */
+ * (vec_environment.h:38-44): env i gets seed + i (u32).  Synchronous.  n_players 1..4 (one player
+ * is a supported batch: the turn passes back to the same player); max_steps 0 ends every episode at
+ * its first step.  A refused argument (COG_ERR_INVALID) launches nothing and leaves the handle alone. */
 COG_API int cog_env_reset(cog_env *env, uint32_t seed, uint8_t n_players, uint8_t n_pieces,
                           int32_t difficulty, uint32_t max_steps, int32_t render);
 /* vec_cog_env::reset() (vec_environment.h:32-36): keep params, continue each env's rng. */

@@ -14,6 +14,9 @@
  *                                          reset_default and auto-reset on again; and host actions past
  *                                          their heads, clamped to (21, 21, 21, 6, 18) as the engine
  *                                          documents (COG_HAZ_BAD_ACTION), in a tenth of the slots
+ *   oracle/_asan/harness_asan --corners    the scenarios of kCornerScen (tests/test_corners_cpu.py): max_steps 0
+ *                                          (a reset with map generation for every env at every step) and 1,
+ *                                          and one player (the turn passes back to the same player)
  *
  * Scenarios: the reference trace sets of tests/golden/ref_traces (oracle/gen_golden.py traces():
  * the stored-mask driver with auto-resets, B-start seeds, 2 and 3 players, the selected-mask
@@ -57,6 +60,14 @@ static const scenario kDriverScen[] = {
     {"clamped_host_actions_sto", 78, 2, 3, 1, 12, 78, 1, 300, 16, 0, 1},
 };
 
+static const scenario kCornerScen[] = {
+    {"sto_hard_ms0_4p", 77, 4, 3, 2, 0, 77, 1, 40, 16, 0, 0},
+    {"sto_hard_ms1_4p", 77, 4, 3, 2, 1, 77, 1, 120, 16, 0, 0},
+    {"sel_hard_ms1_3p", 77, 3, 3, 2, 1, 77, 0, 120, 16, 0, 0},
+    {"sto_hard_1p_ms8", 77, 1, 3, 2, 8, 77, 1, 300, 16, 0, 0},
+    {"sel_hard_1p_1piece", 177, 1, 1, 2, 100000, 177, 0, 1000, 16, 0, 0},
+};
+
 static uint64_t fnv(uint64_t h, const void *p, size_t b) {
   const uint8_t *c = (const uint8_t *)p;
   for (size_t k = 0; k < b; k++) h = (h ^ c[k]) * 0x100000001b3ull;
@@ -73,8 +84,11 @@ int main(int argc, char **argv) {
   }
   int bad = 0;
   const int drivers = argc > 1 && !strcmp(argv[1], "--drivers");
-  const scenario *list = drivers ? kDriverScen : kScen;
-  const size_t n_list = drivers ? sizeof(kDriverScen) / sizeof(kDriverScen[0]) : sizeof(kScen) / sizeof(kScen[0]);
+  const int corners = argc > 1 && !strcmp(argv[1], "--corners");
+  const scenario *list = drivers ? kDriverScen : corners ? kCornerScen : kScen;
+  const size_t n_list = drivers   ? sizeof(kDriverScen) / sizeof(kDriverScen[0])
+                        : corners ? sizeof(kCornerScen) / sizeof(kCornerScen[0])
+                                  : sizeof(kScen) / sizeof(kScen[0]);
   for (size_t q = 0; q < n_list; q++) {
     const scenario *sc = &list[q];
     orc_vec *v = orc_create(sc->n);

@@ -18,6 +18,7 @@ env i of a batch == a 1-env batch seeded seed+i, sampler seeded sseed+i).
     python oracle/gen_golden.py --workloads  # ref_workloads.{npz,json} only
     python oracle/gen_golden.py --lategame   # ref_lategame.json + ref_lategame_digests.npz only
     python oracle/gen_golden.py --bigmaps    # ref_maps_big.json only
+    python oracle/gen_golden.py --corners    # ref_corners.json + ref_corners_digests.npz only
 """
 from __future__ import annotations
 
@@ -55,7 +56,10 @@ def screen(seed, np_, npc, diff, max_steps, sseed, mode, steps):
         return -1
     for t in range(steps):
         s.sample(masks_of(o, mode))
-        o.step(s.actions)
+        try:
+            o.step(s.actions)
+        except RuntimeError:                                 # (a failed map generation at an auto-reset)
+            return t
         if o.flags(0) & po.REF_UNSAFE:
             return t
     return steps
@@ -348,6 +352,56 @@ def bigmaps():
     print(f"bigmaps: {len(out)} reference maps, {len(off)} off-lattice ones")
 
 
+# The corners of the reset parameters, pinned by the reference: one player (the turn passes back to
+# the same player) and max_steps 0..3 (an episode ends at its first step, or at one of its first
+# turn ends).  Every env runs to one step before its first REF_UNSAFE flag or failed map generation
+# on the oracle: with fewer than 4 players every second reset is a B start, which the reference
+# built here cannot run, so those groups screen 64 seeds and keep the ones that run 8 steps or more.
+# (name, n_players, n_pieces, max_steps, mode, steps, first seed, seeds screened, seeds kept, least steps)
+def corner_groups():
+    g = [("solo_1piece_sto", 1, 1, 100000, "sto", 2000, 9100, 64, 4, 2000),
+         ("solo_1piece_sel", 1, 1, 100000, "sel", 1000, 9200, 64, 4, 1000),
+         ("solo_3pieces_ms30_sto", 1, 3, 30, "sto", 600, 9300, 256, 4, 600)]
+    for ms in (0, 1, 2, 3):
+        for mode in ("sto", "sel"):
+            g.append((f"p4_1piece_ms{ms}_{mode}", 4, 1, ms, mode, 80, 9400 + 10 * ms, 64, 8, 80))
+    for players in (3, 2, 1):
+        for ms in (1, 2, 3):
+            mode = "sel" if (players + ms) % 2 else "sto"
+            g.append((f"p{players}_3pieces_ms{ms}_{mode}", players, 3, ms, mode, 24, 9500 + 100 * players + 10 * ms, 64, 64, 8))
+    return g
+
+
+def corners():
+    sets, arrays = [], {}
+    for name, np_, npc, ms, mode, steps, seed, screened, keep, least in corner_groups():
+        envs, digs = [], []
+        for i in range(screened):
+            if len(envs) == keep:
+                break
+            L = screen(seed + i, np_, npc, 2, ms, seed + i, mode, steps)
+            if L < least:
+                continue
+            dig, resets = ref_trace(seed + i, np_, npc, 2, ms, seed + i, mode, L)
+            digs.append(np.frombuffer(b"".join(dig), dtype=np.uint8).reshape(-1, 8))
+            envs.append(dict(index=i, steps=L, resets=resets))
+        assert envs and (keep == screened or len(envs) == keep), f"{name}: {len(envs)} seeds of {screened} run {least} steps"
+        print(f"corners: {name}: {len(envs)} envs, {sum(e['steps'] for e in envs)} reference steps, "
+              f"{sum(e['resets'] for e in envs)} episode ends")
+        arrays[name] = np.concatenate(digs)                  # (one array per set: 347 zip members cost 100 KB)
+        sets.append(dict(name=name, seed=seed, n_players=np_, n_pieces=npc, difficulty=2, max_steps=ms, sampler_seed=seed,
+                         mode=mode, index=[e["index"] for e in envs], steps=[e["steps"] for e in envs],
+                         resets=[e["resets"] for e in envs]))
+    np.savez(os.path.join(OUT, "ref_corners_digests.npz"), **arrays)
+    with open(os.path.join(OUT, "ref_corners.json"), "w") as f:
+        json.dump(dict(source="oracle/_ref (unmodified reference core) via oracle/gen_golden.py --corners",
+                       digest="sha256[:8] over named leaves of obs, sel, rewards, dones, agent_sel, infos, actions",
+                       digests_file="ref_corners_digests.npz (key <set>: the envs of the set one after another, each "
+                                    "uint8[steps[k] + 1, 8]: after reset, then after every step); env k of a set: seed + "
+                                    "index[k], sampler seed + index[k]; resets[k]: its episode ends",
+                       sets=sets), f)
+
+
 def main():
     assert po.ref_available(), "build the reference first: make -C oracle ref"
     os.makedirs(OUT, exist_ok=True)
@@ -359,6 +413,9 @@ def main():
         return
     if "--lategame" in sys.argv:
         lategame()
+        return
+    if "--corners" in sys.argv:
+        corners()
         return
     t = traces()
     arrays = {}

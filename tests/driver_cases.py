@@ -118,7 +118,7 @@ class Harness:
         self.orc, self.osm = po.OracleVec(n), po.OracleSampler(n, sampler_seed)
         self.last = np.zeros(n, dtype=po.ACTION)             # what the sampler's device actions hold
         self.logits = logits_table(n)
-        self.autoreset, self.players = True, 4
+        self.autoreset, self.players, self.max_steps = True, 4, 100000
         self.views, self.acts_fresh = not lazy_views, False
         self.bad_ever = np.zeros(n, dtype=bool)
         self.done_prev = np.zeros(n, dtype=bool)
@@ -197,10 +197,11 @@ class Harness:
 
     def _trio_model(self, steps, chunk):
         """EnvShard::cdeck_ok as runner_launch_fused leaves it, and how the trio launches of this
-        rollout were entered (selected masks, >= 3 players, a chunk > 1: the trio at every size)."""
+        rollout were entered (selected masks, >= 3 players, max_steps >= 1, a chunk > 1: the trio at
+        every size)."""
         if not steps:
             return
-        if chunk > 1 and self.players >= 3:
+        if chunk > 1 and self.players >= 3 and self.max_steps:
             launches = -(-steps // chunk)
             self.trio_loaded += launches - (0 if self.cdeck else 1)
             self.trio_clear += 0 if self.cdeck else 1
@@ -221,7 +222,7 @@ class Harness:
                 self.orc.reset_threaded(seed, players, pieces, difficulty, max_steps, self.threads)
             else:
                 self.orc.reset(seed, players, pieces, difficulty, max_steps)
-            self.players, self.cdeck = players, False
+            self.players, self.max_steps, self.cdeck = players, max_steps, False
         elif name == "X0":
             if eng:
                 self.env.reset()

@@ -144,6 +144,13 @@ def arrays(w):
 
 # ---- recorded from the oracle (the engine matches it bit for bit) ------------------------------
 REC = dict(n=200, T=96, max_steps=6, reset_seed=5, sampler_seed=7, pieces=3, difficulty=2)
+# one player (seat 0 alone: per-seat GAE is the textbook form): a turn is never shorter, so that REC's
+# window holds 0 to 4 episode ends per env; at max_steps 7 from seed 6 it holds 1 to 3, as check_oracle_window asks
+REC_SOLO = dict(REC, max_steps=7, reset_seed=6)
+
+
+def rec(players):
+    return REC_SOLO if players == 1 else REC
 
 
 @functools.lru_cache(maxsize=None)
@@ -153,7 +160,7 @@ def oracle_window(players):
     import pyoracle as po
     n, T = REC["n"], REC["T"]
     orc, osm = po.OracleVec(n), po.OracleSampler(n, REC["sampler_seed"])
-    orc.reset(REC["reset_seed"], players, REC["pieces"], REC["difficulty"], REC["max_steps"])
+    orc.reset(rec(players)["reset_seed"], players, REC["pieces"], REC["difficulty"], rec(players)["max_steps"])
     agents = np.zeros((T, n), dtype=np.uint8)
     dones = np.zeros((T, n), dtype=np.uint8)
     rewards = np.zeros((T, n, 4), dtype=np.float32)
@@ -203,7 +210,7 @@ def all_gpu_inputs(with_oracle=True):
         for gamma, lam in PARAMS:
             yield f"random T={T} n={n} gamma={gamma} lam={lam}", arrays(w), dict(last_values=w["last_values"], gamma=gamma, lam=lam)
     if with_oracle:
-        for players in (4, 3, 2):
+        for players in (4, 3, 2, 1):
             c = recorded_case(players)
             yield (f"recorded, {players} players", (c["values"], c["agents"], c["planted"], c["dones"]),
                    dict(last_values=c["last_values"]))

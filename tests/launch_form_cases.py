@@ -49,20 +49,31 @@ REDO_SEQ = [X(77, 4, 8), T20, T20, T20, X(77, 4, 100000), T20, T20, T20]
 HOST_SEQ = [X(77, 4, 8), ("H", P), ("Hc", P), ("Hs", P), ("R1", P), ("Rr", 5), ("Th20", P), ("L", P), ("Ls", P),
             ("H", P), T20, ("H", P)]
 HOST_TWO_SHARD_N = 301
+# the reset-parameter corners (tests/corner_cases.py): max_steps 0 (launches of 20 + 4, 8 and 8 steps: every env
+# ends at every step, 8,000 oracle resets at n = 200; 4 players take the kernels of 2 there), 3 players at
+# max_steps 1 (the trio, an end at every turn end), one player at max_steps 8 and 2 (the next agent is the
+# acting agent)
+P0 = 24
+CORNERS_SEQ = [X(77, 4, 0), ("T20", P0), ("S20", 8), ("T20", 8), X(78, 3, 1), T20, S20, T20,
+               X(79, 1, 8), T20, S20, T20, ("H", 5), X(80, 1, 2), T20, S20, "C"]
+# the host walk after a reset with one player (at the row's n) and at max_steps 0 (70 envs, 8 steps per op)
+CORNERS_HOST_MS0_N, CORNERS_HOST_MS0_STEPS = 70, 8
+CORNERS_HOST_SEQS = {"one player": [X(77, 1, 8)] + HOST_SEQ[1:],
+                     "max_steps 0": [X(77, 4, 0)] + [(d, min(k, CORNERS_HOST_MS0_STEPS)) for d, k in HOST_SEQ[1:]]}
 
 
 class Row:
     """env: the switches; sizes: the batch sizes it runs at; seq: "rollout" | "rollout+2p" | "redo" |
-    "big" | "host"; kinds: what rollout_kind must say for (players, stored) -> name."""
+    "big" | "host" | "corners" | "corners-host"; kinds: what rollout_kind must say for (players, stored) -> name."""
 
     def __init__(self, name, env, seq="rollout", sizes=SIZES, kinds=None):
         self.name, self.env, self.seq, self.sizes = name, dict(env), seq, tuple(sizes)
         self.kinds = kinds if kinds is not None else {(4, False): "trio", (3, False): "trio", (2, False): "duo",
-                                                      (4, True): "duo"}
+                                                      (4, True): "duo", (1, False): "duo", (1, True): "duo"}
 
 
 def _all(kind):
-    return {(p, s): kind for p in (4, 3, 2) for s in (False, True)}
+    return {(p, s): kind for p in (4, 3, 2, 1) for s in (False, True)}
 
 
 ROWS = {r.name: r for r in (
@@ -86,6 +97,17 @@ ROWS = {r.name: r for r in (
     Row("host-no-zerocopy", {"COG_NO_ZEROCOPY": "1"}, seq="host", sizes=(200,)),
     Row("host-no-hbm-masks", {"COG_NO_HBM_MASKS": "1"}, seq="host", sizes=(200,)),
     Row("host-no-spec", {"COG_NO_SPEC": "1"}, seq="host", sizes=(200,)),
+    # one player and max_steps 0..2 under the forms (one player selects like two: never the trio)
+    Row("corners-default", {}, seq="corners"),
+    Row("corners-no-lat", {"COG_TRIO_JT": "0"}, seq="corners"),
+    Row("corners-epw32", {"COG_TRIO_EPW": "32"}, seq="corners"),
+    Row("corners-wpc1", {"COG_TRIO_WPC": "1"}, seq="corners"),
+    Row("corners-duo", {"COG_TRIO": "0"}, seq="corners",
+        kinds={(4, False): "duo", (3, False): "duo", (2, False): "duo", (4, True): "duo", (1, False): "duo", (1, True): "duo"}),
+    Row("corners-pipe", {"COG_ROLLOUT": "pipe"}, seq="corners", kinds=_all("pipe")),
+    Row("corners-wave", {"COG_ROLLOUT": "wave"}, seq="corners", kinds=_all("wave")),
+    Row("corners-host-no-zerocopy", {"COG_NO_ZEROCOPY": "1"}, seq="corners-host", sizes=(200,)),
+    Row("corners-host-no-spec", {"COG_NO_SPEC": "1"}, seq="corners-host", sizes=(200,)),
 )}
 CASES = [(r.name, n) for r in ROWS.values() for n in r.sizes]
 SWITCHES = sorted({k for r in ROWS.values() for k in r.env} | {"COG_SPIN_US", "COG_RUNNER_CHUNK", "COG_DEBUG_PARK_NOFIX"})
@@ -100,6 +122,10 @@ def sequence_of(row):
         return list(REDO_SEQ)
     if row.seq == "big":
         return list(dc.BIG_CASES["T20_S50_T20"])
+    if row.seq == "corners":
+        return list(CORNERS_SEQ)
+    if row.seq == "corners-host":
+        return list(CORNERS_HOST_SEQS["one player"])
     return list(HOST_SEQ)
 
 
@@ -149,14 +175,18 @@ def child_main(argv):
     C = cg._city_of_gold
     shard_n = n
     form = C.trio_form(shard_n)
-    kinds = {f"{p},{int(s)}": C.rollout_kind(shard_n, p, s) for p in (4, 3, 2) for s in (False, True)}
+    kinds = {f"{p},{int(s)}": C.rollout_kind(shard_n, p, s) for p in (4, 3, 2, 1) for s in (False, True)}
     check_form(row, n, form, kinds)
     out = dict(row=row.name, n=n, form=form, kinds=kinds)
     seq = sequence_of(row)
-    if row.seq == "host":
+    if row.seq in ("host", "corners-host"):
         spec_off = "COG_NO_SPEC" in row.env
-        for what, kw, hn, s in (("one shard", {}, n, seq), ("two shards", {"device": [0, 0]}, HOST_TWO_SHARD_N, seq),
-                                ("lazy views", {"lazy_views": True}, dc.PAIR_N, dc.LAZY_VIEWS_CASE)):
+        walks = (("one shard", {}, n, seq), ("two shards", {"device": [0, 0]}, HOST_TWO_SHARD_N, seq),
+                 ("lazy views", {"lazy_views": True}, dc.PAIR_N, dc.LAZY_VIEWS_CASE))
+        if row.seq == "corners-host":
+            walks = (("one player", {}, n, seq), ("max_steps 0", {}, CORNERS_HOST_MS0_N, CORNERS_HOST_SEQS["max_steps 0"]))
+            out["ends"] = 0
+        for what, kw, hn, s in walks:
             h = dc.Harness(cg, hn, dc.PAIR_SEED, **kw)
             assert h.env.num_shards == (2 if what == "two shards" else 1)
             for k, op in enumerate(s):
@@ -170,8 +200,12 @@ def child_main(argv):
                 elif what == "one shard" and k == 1 and not row.env:     # (single-shard samplers speculate)
                     assert hits > 0, f"{what}: no speculative sample taken in {op!r}"
             h.compare_hazards(what + ", at the end")
-            if s is seq:
+            if s is not dc.LAZY_VIEWS_CASE:
                 assert all(e >= 1 for e in h.op_ends[1:]), f"{what}: an op without an episode end: {h.op_ends}"
+            if what == "max_steps 0":
+                assert h.op_ends[1:] == [hn * k for _, k in s[1:]], f"{what}: not every env ends at every step: {h.op_ends}"
+            if row.seq == "corners-host":
+                out["ends"] += h.ends
             out[what.replace(" ", "_") + "_spec_hits"] = int(h.smp.spec_stats()[1])
     else:
         threads = po.host_threads() if n > 4096 else 0

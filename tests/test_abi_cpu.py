@@ -123,7 +123,7 @@ def test_rollout_kind_selection():
     """cog_rollout_kind (a host-only query, no device needed): the selected-mask loop with >= 3
     players takes the trio rollout at every shard size; the stored masks and 2-player batches keep
     round 3's kernels by size (duo <= 16,384, pipe <= 32,768, wave above: cog_engine.hip
-    rollout_kind)."""
+    rollout_kind); one player selects like two, for both mask sources."""
     if os.environ.get("COG_ROLLOUT") or os.environ.get("COG_TRIO"):
         pytest.skip("rollout kind forced by the environment")
     lib = ctypes.CDLL(LIB)
@@ -131,7 +131,11 @@ def test_rollout_kind_selection():
     TRIO, DUO, WAVE, PIPE = 3, 0, 1, 2
     for n in (64, 4096, 8192, 16384, 32768, 53752, 65536, 131072):
         assert kind(n, 4, 0) == TRIO and kind(n, 3, 0) == TRIO
-    for p, stored in ((2, 0), (4, 1), (3, 1)):
+    for n in (1, 33, 64, 200):
+        assert kind(n, 1, 0) == DUO and kind(n, 1, 1) == DUO and kind(n, 2, 0) == DUO
+    assert kind(16385, 1, 0) == PIPE and kind(16385, 1, 1) == PIPE
+    assert kind(32769, 1, 0) == WAVE and kind(32769, 1, 1) == WAVE
+    for p, stored in ((2, 0), (4, 1), (3, 1), (1, 0), (1, 1), (2, 1)):
         assert kind(8192, p, stored) == DUO and kind(16384, p, stored) == DUO
         assert kind(24576, p, stored) == PIPE and kind(32768, p, stored) == PIPE
         assert kind(65536, p, stored) == WAVE

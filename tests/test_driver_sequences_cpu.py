@@ -341,7 +341,7 @@ def test_launch_form_rows_cover_the_forms():
     from city_of_gold import _city_of_gold as C
     for n in (200, 33, lf.BIG_N):
         form = C.trio_form(n)
-        kinds = {f"{p},{int(s)}": C.rollout_kind(n, p, s) for p in (4, 3, 2) for s in (False, True)}
+        kinds = {f"{p},{int(s)}": C.rollout_kind(n, p, s) for p in (4, 3, 2, 1) for s in (False, True)}
         assert form["cus"] == 256 or C.device_count() > 0
         if n != lf.BIG_N:
             lf.check_form(lf.ROWS["default"], n, form, kinds)

@@ -26,6 +26,13 @@ checks again.
                    views first touched after device work, under COG_NO_ZEROCOPY (the staged publish),
                    COG_NO_HBM_MASKS (masks sampled over PCIe) and COG_NO_SPEC (spec_stats()[1] == 0;
                    > 0 after the first H without a switch)
+  corners-*        the reset-parameter corners (tests/corner_cases.py) under the forms: 4 players at max_steps 0
+                   (every env ends at every step; such a batch keeps off the trio), 3 players at
+                   max_steps 1 (the trio: an end at every turn end), one player at max_steps 8 and 2,
+                   each as T20 S20 T20, with no switch, COG_TRIO_JT=0, COG_TRIO_EPW=32, COG_TRIO_WPC=1,
+                   COG_TRIO=0 and COG_ROLLOUT=pipe / wave (one player selects like two: rollout_kind is
+                   asserted for 1 player too); the host walk after a reset with one player and (70
+                   envs, 8 steps per op) at max_steps 0 under COG_NO_ZEROCOPY and COG_NO_SPEC
   encode           env.time_encode(1, variant) for the production kernel (0), k_encode_lds<false> (1)
                    and k_encode_direct (2): observations equal their copy and the oracle; then the
                    map bytes of the device records are overwritten with 0xEE and the kernel must put
@@ -45,6 +52,8 @@ their 2-player tail, the longest); redo 0.61-0.72 s; a host row (three harnesses
 1.70-1.85 s; lat-shared-cu at 16,385 envs 1.73-1.79 s, within the 1.2-3.2 s of the big cases of
 test_gpu_driver_sequences.py; an encode case 0.01-0.25 s (the first one brings torch's GPU side up).
 45 cases, 29 s together.
+The 16 corners-* rows: 3.4-3.6 s at n = 200 (8,000 oracle resets at max_steps 0), 0.9-1.3 s at 33, the two host
+rows 2.3-2.5 s; 37 s together.
 
 That the cases bite, tried on three scratch builds of the engine (never committed), the whole GPU suite
 run against each; every edit keeps its addresses in range and gives wrong bytes:

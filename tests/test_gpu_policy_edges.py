@@ -2,7 +2,7 @@
 tests/test_gpu_policy_sampler.py and tests/test_gpu_policy_evaluate.py never reach: sampled indices
 known exactly (flat heads, planted draws at u = 0, j / 4 and 1 - 2^-24), logits far outside [-8, 8],
 unlikely recorded actions, a recorded action on a valid -inf entry, arbitrary non-zero mask bytes,
-and the stored masks of 2 and 3 players.  The inputs and the allowances come from
+and the stored masks of 1, 2 and 3 players.  The inputs and the allowances come from
 tests/policy_cases.py; tests/test_policy_edges_cpu.py pins them with the numpy references alone.
 
 Allowances: entropy 1e-5; logp 1e-5 + 8 2^-24 |ref|; a float32 gradient row 1e-5 (|g_lp| + |g_en|); a
@@ -290,9 +290,9 @@ def test_any_non_zero_mask_byte_is_valid(cg):
         check_sampler(ref, *out[1][:3], f"mask bytes {kind_id(kind)}")
 
 
-@pytest.mark.parametrize("players", [2, 3])
+@pytest.mark.parametrize("players", [2, 3, 1])
 def test_stored_masks_of_fewer_players(cg, players):
-    """20 steps of sample_policy(logits, env, "stored") -> step_device with 2 and 3 players: the actions
+    """20 steps of sample_policy(logits, env, "stored") -> step_device with 2, 3 and 1 players: the actions
     are legal under the current agent's stored mask as it was before the step and follow the index
     rule; every player takes a turn within the 20 steps.
 

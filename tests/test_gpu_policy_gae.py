@@ -171,7 +171,7 @@ def record_engine(cg, players):
     n, T = gr.REC["n"], gr.REC["T"]
     env = cg.vec.get_vec_env(n)()
     smp = cg.vec.get_vec_sampler(n)(gr.REC["sampler_seed"])
-    env.reset(gr.REC["reset_seed"], players, gr.REC["pieces"], cg.HARD, gr.REC["max_steps"], False)
+    env.reset(gr.rec(players)["reset_seed"], players, gr.REC["pieces"], cg.HARD, gr.rec(players)["max_steps"], False)
     runner = cg.vec.get_runner(n)(env, smp, None, device_views=True, stored_masks=True)
     views = cg.device_tensors(env)
     agents, dones, rewards = [], [], []
@@ -186,7 +186,7 @@ def record_engine(cg, players):
     return torch.stack(agents), torch.stack(dones), torch.stack(rewards)
 
 
-@pytest.mark.parametrize("players", (4, 3, 2))
+@pytest.mark.parametrize("players", (4, 3, 2, 1))
 def test_recorded_from_the_engine(cg, players):
     import torch
     orc = gr.oracle_window(players)

@@ -146,3 +146,32 @@ def test_action_sampler_matches_vec_sampler(cg):
         assert act == v.get_actions()[0]
         rec = cg.ActionData(play=act.play)
         assert rec.play == act.play and np.dtype(cg.ActionData).itemsize == 64
+
+
+def test_one_player_unit_loop_against_the_oracle(cg):
+    """The unit loop with one player (the turn passes back to the same player: k_env_step's
+    `na == ag` stores), 400 steps against a 1-env oracle without the vec wrapper's auto-reset:
+    the episode ends at max_steps 30 on the way and the steps after it are dead steps."""
+    env, obs, info, rewards, mask = bound_env(cg)
+    env.reset(54321, 1, 3, cg.HARD, 30, False)
+    orc, osm = po.OracleVec(1), po.OracleSampler(1, 42)
+    orc.reset(54321, 1, 3, 2, 30)
+    orc.set_autoreset(False)
+    smp = cg.vec.get_vec_sampler(1)(42)
+    assert env.get_n_players() == 1 and po.named_equal(obs, orc.observations) is None
+    done_at = None
+    for t in range(400):
+        assert env.agent_selection == 0
+        smp.sample(np.ascontiguousarray(obs[0]["player_data"][0]["action_mask"]).reshape(1))
+        osm.sample(po.stored_masks(orc))
+        assert po.named_equal(smp.get_actions(), osm.actions) is None, f"actions differ at step {t}"
+        env.step(smp.get_actions())
+        orc.step(osm.actions)
+        for nm, a, b in (("observations", obs, orc.observations), ("mask", mask, orc.selected_action_masks),
+                         ("info", info, orc.infos)):
+            bad = po.named_equal(a, b)
+            assert bad is None, f"{nm}.{bad} differs from the oracle at step {t}"
+        assert np.array_equal(rewards, orc.rewards[0]) and bool(env.get_done()) == bool(orc.dones[0]), f"step {t}"
+        if done_at is None and env.get_done():
+            done_at = t
+    assert done_at is not None and 30 <= done_at < 300 and info[0]["total_length"] == 30

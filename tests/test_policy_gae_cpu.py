@@ -97,7 +97,7 @@ def test_gpu_windows_hold_their_cases():
 
 
 def test_oracle_window_meets_the_recorded_tests_conditions():
-    for players in (4, 3, 2):
+    for players in (4, 3, 2, 1):
         gr.check_oracle_window(gr.oracle_window(players), players)
 
 
