@@ -207,7 +207,7 @@ int launch_rollout(const DevState &s, int mask_source, int steps, uint32_t *d_rn
                    void *stream, bool defer_ok, uint32_t *park_seq, bool no_fixup = false);
 inline size_t park_list_bytes(size_t n) { return (2 + (n + 31) / 32) * sizeof(uint32_t); }
 int rollout_kind_of(size_t n, int mask_source, bool defer_ok);   // 0 duo, 1 wave, 2 pipe, 3 trio
-int trio_epw(size_t n);                                          // envs per trio workgroup (32 or 64)
+int trio_epw();                                                  // envs per trio workgroup (32 or 64)
 // the form of the trio launch over a shard of n envs on `device` (cog.h cog_trio_form): envs per
 // workgroup, workgroups, the LAT form, workgroups per CU the LDS pad keeps (0: no pad) and the pad's
 // bytes, k_env_fixup's grid, the device's CUs -- from the helpers launch_rollout itself calls

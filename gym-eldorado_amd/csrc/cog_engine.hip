@@ -11,19 +11,28 @@
 // (rot+1: (x, y) -> (-y, x + y), the exact value of geometry.cpp:3-17 + map.cpp:17-37 on this
 // lattice) and overlap tests use the occupancy grid instead of sort+merge (map.cpp:53-74).
 //
-// Kernels:
+// In text order: the byte-record rules, map generation (one env per work-item, then by a whole wave), the
+// encode, the mask bit-vectors and the sampler, the register-resident step, the lane drivers, the rollouts
+// (parts under engine/), the small kernels, the host launchers.  Kernels:
 //   k_init           default-construct N envs (vec_environment.h:23-30)
 //   k_reset          cog_env::reset(params) incl. procedural map generation (map.cpp:697-742)
-//   k_encode         48x48x7 map-observation encode (map.cpp:389-405): streaming, 16 cells / item
-//   k_sample         masked uniform sampler (sampler.h:14-79)
+//   k_encode_lds, k_encode_direct   48x48x7 map-observation encode (map.cpp:389-405): 16 cells / item
 //   k_env_step<SRC>  vec_cog_env::step with auto-reset (vec_environment.h:46-61); SRC: host
 //                    actions, or the runner-fused sample(selected | stored masks) + step
-//                    (runner.h:46-55)
-//   k_sync_heads     mask bit-vectors of every env from its byte records (init / reset)
+//                    (runner.h:46-55); k_env_step_pub<SRC> also publishes to the host views
+//   k_env_rollout, k_env_rollout_pipe   K x (sample; step) per launch, a wave per 64 envs (engine/rollout_wave.h)
+//   k_env_rollout_duo                   a stepping and a storing wave (engine/rollout_duo.h)
+//   k_env_rollout_trio                  stepping, drawing and two storing waves (engine/rollout_trio.h)
+//   k_env_fixup      the envs a duo / trio launch parked
+//   k_sample         masked uniform sampler (sampler.h:14-79)
+//   k_publish        changed granules of the host-visible records to the pinned views
+//   k_sync_heads, k_resync   mask bit-vectors of every env from its byte records (init / reset)
+//   k_signal, k_seed_sampler, k_copy_peak / _block / _one, k_stream_mix   completion word, sampler seeds, copy probes
 //
-// One translation unit on purpose (the step inlines into every driver; one two-minute compile).
-// The trio rollout is a part of its own, engine/rollout_trio.h, included where it stood; a change
-// that moves text only shows that with tools/devcode_same.sh <git-rev> (same device code bytes).
+// One translation unit on purpose (the step inlines into every driver; one two-minute compile): the
+// parts are not separately compilable.  The order of the text, and of the launchers' first mention of
+// each kernel template's instance, fixes the code object's layout; a change that moves text only shows
+// that with tools/devcode_same.sh <git-rev> (same device code bytes).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdlib>
@@ -2673,823 +2682,12 @@ __global__ void __launch_bounds__(64) k_env_step_pub(DevState s, const uint8_t *
   }
 }
 
-// Persistent rollout: K x (sample; step) per launch (the runner's device loop, runner.h:46-55).
-// Every step stores its outputs exactly as a single-step launch does (the HBM state after each
-// step is the reference's); what changes is where the next step reads its inputs from: the
-// env-level records stay in VGPRs and every player's records (deck, counters, neighbourhood
-// cache, stored mask) in this wave's LDS, so a step issues no global loads unless it resets.
-template <int NL>                     // NL: envs (lanes) per workgroup
-struct LaneLds {
-  uint4 deck[4][7][NL];               // [player][granule][lane]: lane-contiguous, conflict-free
-  uint4 pl[4][NL];
-  uint2 cells[4][NL];
-  uint4 heads[4][NL];                 // stored masks (MBits + pad)
-  UidEntry tab[kUidTab];              // the uniform's division table
-};
-template <class LaneLds>
-DEV void lds_fill_players(LaneLds &L, const DevState &s, size_t i, int l) {
-  const uint4 *pv4 = reinterpret_cast<const uint4 *>(s.priv + i);
-#pragma unroll
-  for (int p = 0; p < 4; p++) {
-    const uint4 *dk = reinterpret_cast<const uint4 *>(deck_ptr(s, i, p));
-#pragma unroll
-    for (int k = 0; k < 7; k++) L.deck[p][k][l] = dk[k];
-    L.pl[p][l] = pv4[4 + p];
-    L.cells[p][l] = reinterpret_cast<const uint2 *>(pv4 + 8)[p];
-    L.heads[p][l] = s.heads[5 * i + 1 + p];
-  }
-}
-// The wave's player records are stored cooperatively at the end of a launch: consecutive
-// work-items take consecutive 16-B granules of one env's records (its counters and neighbourhood
-// caches are EnvPriv granules 4..9, its stored-mask bit vectors 4 consecutive heads), so one
-// store instruction covers a few contiguous runs instead of 64 envs' scattered granules.
-// Measured (profiles/r02_b_fixedcost.txt): the per-work-item store cost 6.2 us per launch at
-// 65,536 envs, this one about 1 us.  The same transposition for the launch's loads was slower (19.7 against
-// 9.5 us): those stay one env per work-item (lds_fill_players).  ne = the wave's envs; a
-// work-item past the end of a ragged last wave stores env ne - 1's records again.
-template <class LaneLds, int NL>
-DEV void lds_store_wave(const LaneLds &L, const DevState &s, size_t base, int ne) {
-  const int l = threadIdx.x;                               // (past the end: env ne - 1's records again)
-#pragma unroll
-  for (int j = 0; j < 4 * NL / 64; j++) {
-    const int f = j * 64 + l, e = min(f >> 2, ne - 1), q = f & 3;
-    reinterpret_cast<uint4 *>(s.priv + base + e)[4 + q] = L.pl[q][e];
-  }
-#pragma unroll
-  for (int j = 0; j < 2 * NL / 64; j++) {
-    const int f = j * 64 + l, e = min(f >> 1, ne - 1), q = f & 1;
-    const uint2 a = L.cells[2 * q][e], b = L.cells[2 * q + 1][e];
-    reinterpret_cast<uint4 *>(s.priv + base + e)[8 + q] = make_uint4(a.x, a.y, b.x, b.y);
-  }
-#pragma unroll
-  for (int j = 0; j < 4 * NL / 64; j++) {
-    const int f = j * 64 + l, e = min(f >> 2, ne - 1), p = f & 3;
-    s.heads[5 * (base + e) + 1 + p] = L.heads[p][e];
-  }
-}
-// the env-level private records of env i (EnvPriv granules 0, 1, 3, the selected mask's bits)
-DEV void store_env_private(const DevState &s, size_t i, const Snap &S) {
-  uint4 *pw = reinterpret_cast<uint4 *>(s.priv + i);
-  pw[0] = S.g0;
-  pw[1] = S.g1;
-  reinterpret_cast<uint32_t *>(pw + 3)[0] = S.info_steps;
-  s.heads[5 * i] = mbits_u4(S.sel);
-}
-// every private record of env i (EnvPriv granules 0, 1, 3, all players, all mask bit vectors)
-// from the rollout's on-chip copies
-template <class LaneLds>
-DEV void store_private_all(const DevState &s, size_t i, const Snap &S, const LaneLds &L, int l) {
-  uint4 *pw = reinterpret_cast<uint4 *>(s.priv + i);
-  pw[0] = S.g0;
-  pw[1] = S.g1;
-  reinterpret_cast<uint32_t *>(pw + 3)[0] = S.info_steps;
-  s.heads[5 * i] = mbits_u4(S.sel);
-#pragma unroll
-  for (int p = 0; p < 4; p++) {
-    pw[4 + p] = L.pl[p][l];
-    reinterpret_cast<uint2 *>(pw + 8)[p] = L.cells[p][l];
-    s.heads[5 * i + 1 + p] = L.heads[p][l];
-  }
-}
-template <class LaneLds>
-DEV void lds_players(const LaneLds &L, int l, int ag, int na, Snap &S) {
-  S.pla = L.pl[ag][l];
-  S.pln = L.pl[na][l];
-  S.ca = L.cells[ag][l];
-  S.cn = L.cells[na][l];
-  S.sta = mbits_of(L.heads[ag][l]);
-  S.stn = mbits_of(L.heads[na][l]);
-#pragma unroll
-  for (int k = 0; k < 7; k++) S.dk[k] = L.deck[ag][k][l];
-}
-
-// The rollout is one kernel in two passes.  The lean pass (FIX = false) carries no episode-end
-// code: a lane whose env finishes (or starts done) at step t stores its state, keeps t (its
-// "park" code) and leaves the loop; the other lanes go on.  After the loop, a wave with a parked
-// lane runs the fix-up pass (FIX = true, a wave-uniform branch) for exactly those lanes: it
-// completes step t's episode end (finish_episode, dones, auto-reset, encode) and runs the env's
-// remaining steps with the full step (resets included).  Nothing reads the env in between and
-// envs are independent (no barrier between the reference's workers either, runner.h:39-62), so
-// the outputs are those of one full-step loop; the lean loop keeps the reset path's registers
-// out of its allocation.  A wave with nothing parked ends after the lean pass (round 1 launched
-// the fix-up as a second kernel: 4.8 us per launch even when it had nothing to do).
-// park codes: bits 0..29 the step t; kParkFinish: step t finished the episode (else the env
-// started step t done); kParkRedo: step t was not run (the trio's stepping wave met an action
-// outside its lean step, lean_player in trio_stepper) -- the fix-up runs it with the full step
-constexpr uint32_t kParkNone = ~0u, kParkFinish = 1u << 31, kParkRedo = 1u << 30;
-constexpr uint32_t kParkStep = kParkRedo - 1u;
-// The records of a wave's envs seen from the wave's first env: a per-wave (scalar) base and a
-// per-lane index below 64, so that record addresses are a scalar base plus a 32-bit lane offset
-// (the saddr form of global loads and stores) instead of 64-bit products of a global index,
-// which the compiler rematerialises at every store under the kernel's register pressure.
-DEV DevState wave_view(const DevState &s, size_t base) {
-  DevState v = s;
-  v.obs += base * COG_OBS_BYTES;
-  v.sel += base * COG_MASK_BYTES;
-  v.info += base * COG_INFO_BYTES;
-  v.rew += base * 4;
-  v.done += base;
-  v.agent += base;
-  v.priv += base;
-  v.grid += base * (size_t)kGridBytes;
-  v.cgrid += base * COG_CELLS;
-  v.heads += 5 * base;
-  v.cdeck += 10 * base;
-  v.cwide += base;
-  v.gen += base;
-  v.park += base;
-  v.first += base;
-  v.n = s.n > base ? s.n - base : 0;
-  return v;
-}
-// a duo / trio workgroup with a parked env appends its index to the launch's parked list (one
-// atomic per such wave), so that k_env_fixup visits only those (DevState::parkq)
-DEV void park_list_push(const DevState &s_glob, bool parked) {
-  if (__builtin_amdgcn_ballot_w64(parked) && (threadIdx.x & 63) == 0) {
-    if (s_glob.no_fixup) {                                 // the host showed no park could happen
-      atomicOr(&s_glob.status[0], F_PARK_NOFIX);
-      atomicAdd(&s_glob.status[1], 1u);
-      *s_glob.err = 1u;
-    }
-    const uint32_t j = atomicAdd(&s_glob.parkq[s_glob.park_par], 1u);
-    s_glob.parkq[2 + j] = blockIdx.x;
-  }
-}
-// the other counter back to 0 for the next launch (the previous launch's fix-up, which read it,
-// has completed: same stream)
-DEV void park_list_clear_other(const DevState &s_glob) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) s_glob.parkq[s_glob.park_par ^ 1u] = 0u;
-}
-// Two-wave rollout for small shards (k_env_rollout_pipe): the stepping wave hands each step's
-// outputs to a second wave of its workgroup through a double-buffered LDS ring, and the second
-// wave finds what changed and issues the store phase (mask expansions and the granule stores)
-// while the first runs the next step.  One record per lane and step, [buffer][granule][lane]:
-//   0-2   ObsData 16128.. (phase, resources, shop) after the step, 3-5 before it
-//   6-12  the acting player's DeckObs after the step
-//   13    selected-mask bits after, .w = flags: 28 valid, 29 moved, 30 next player != acting
-//         player (the storing wave keeps every player's deck as last stored, DeckImage)
-//   14    acting player's stored-mask bits after, .w = ag | na << 8 | Info steps byte << 16
-//   15    next player's stored-mask bits after
-//   16-18 the three mask bit vectors before the step (9 dwords), then the action (8 bytes)
-//   19    EnvPriv granule 2 (locations) when moved
-constexpr int kOutG = 20;
-struct OutRing {
-  uint4 g[2][kOutG][64];
-};
-DEV void out_record_write(OutRing &O, int b, int l, int ag, int na, const Snap &S, const RegEnv &R,
-                          const uint8_t act[5]) {
-  const uint32_t gm = 1u << 28 | (R.moved ? 1u << 29 : 0u) | (na != ag ? 1u << 30 : 0u);
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    O.g[b][k][l] = make_uint4(R.sh[4 * k], R.sh[4 * k + 1], R.sh[4 * k + 2], R.sh[4 * k + 3]);
-    O.g[b][3 + k][l] = S.sh[k];
-  }
-#pragma unroll
-  for (int k = 0; k < 7; k++) O.g[b][6 + k][l] = make_uint4(R.d[4 * k], R.d[4 * k + 1], R.d[4 * k + 2], R.d[4 * k + 3]);
-  const MBits bs = bits_of(R.sel), ba = bits_of(R.sta), bn = bits_of(R.stn);
-  O.g[b][13][l] = make_uint4(bs.w0, bs.w1, bs.w2, gm);
-  O.g[b][14][l] = make_uint4(ba.w0, ba.w1, ba.w2,
-                             (uint32_t)ag | (uint32_t)na << 8 | ((R.info_steps >> (8 * ag)) & 0xffu) << 16);
-  O.g[b][15][l] = make_uint4(bn.w0, bn.w1, bn.w2, 0u);
-  O.g[b][16][l] = make_uint4(S.sel.w0, S.sel.w1, S.sel.w2, S.sta.w0);
-  O.g[b][17][l] = make_uint4(S.sta.w1, S.sta.w2, S.stn.w0, S.stn.w1);
-  O.g[b][18][l] = make_uint4(S.stn.w2,
-                             (uint32_t)act[0] | (uint32_t)act[1] << 8 | (uint32_t)act[2] << 16 | (uint32_t)act[3] << 24,
-                             (uint32_t)act[4], 0u);
-  O.g[b][19][l] = R.g2;
-}
-DEV uint4 sel4(bool c, const uint4 &a, const uint4 &b) {
-  return make_uint4(c ? a.x : b.x, c ? a.y : b.y, c ? a.z : b.z, c ? a.w : b.w);
-}
-// the storing wave's copy of every player's DeckObs as it stands in HBM (loaded at the start of
-// the launch, then updated by its own stores): the previous value of the acting player's deck
-struct DeckImage {
-  uint4 d[4][7];
-};
-DEV void deck_image_load(DeckImage &I, const DevState &s, size_t i) {
-#pragma unroll
-  for (int p = 0; p < 4; p++) {
-    const uint4 *dk = reinterpret_cast<const uint4 *>(deck_ptr(s, i, p));
-#pragma unroll
-    for (int k = 0; k < 7; k++) I.d[p][k] = dk[k];
-  }
-}
-// the storing wave: exactly the stores store_outputs + store_action issue, in the same order
-DEV void out_record_store(const OutRing &O, int b, int l, const DevState &s, size_t i, uint8_t *actions_out,
-                          DeckImage &I) {
-  const uint4 m = O.g[b][13][l];
-  const uint32_t gm = m.w;
-  if (!((gm >> 28) & 1u)) return;
-  const uint4 x = O.g[b][14][l], o0 = O.g[b][16][l], o1 = O.g[b][17][l], o2 = O.g[b][18][l];
-  const int ag = (int)(x.w & 0xffu), na = (int)((x.w >> 8) & 0xffu);
-  uint8_t *ob = s.obs + i * COG_OBS_BYTES;
-  s.info[i * COG_INFO_BYTES + COG_AGENT_INFO0 + COG_AGENT_INFO_STRIDE * ag] = (uint8_t)(x.w >> 16);
-  if ((gm >> 29) & 1u) reinterpret_cast<uint4 *>(s.priv + i)[2] = O.g[b][19][l];
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const uint4 v = O.g[b][k][l];
-    if (ne4(v, O.g[b][3 + k][l])) reinterpret_cast<uint4 *>(ob + COG_OBS_PHASE)[k] = v;
-  }
-  uint8_t *deck = deck_ptr(s, i, ag);
-#pragma unroll
-  for (int k = 0; k < 7; k++) {
-    const uint4 v = O.g[b][6 + k][l];
-    uint4 old = I.d[3][k];                                 // (selects: a register array indexed
-#pragma unroll                                             // by a lane value would go to scratch)
-    for (int p = 2; p >= 0; p--) old = sel4(ag == p, I.d[p][k], old);
-    if (ne4(v, old)) reinterpret_cast<uint4 *>(deck)[k] = v;
-#pragma unroll
-    for (int p = 0; p < 4; p++) I.d[p][k] = sel4(ag == p, v, I.d[p][k]);
-  }
-  const MBits bs{m.x, m.y, m.z}, ba{x.x, x.y, x.z};
-  store_mask_record(reinterpret_cast<uint4 *>(s.sel + i * COG_MASK_BYTES), bs,
-                    mask_diff_granules(bs, MBits{o0.x, o0.y, o0.z}));
-  store_mask_record(reinterpret_cast<uint4 *>(deck + COG_PD_MASK), ba, mask_diff_granules(ba, MBits{o0.w, o1.x, o1.y}));
-  if ((gm >> 30) & 1u) {
-    const uint4 y = O.g[b][15][l];
-    const MBits bn{y.x, y.y, y.z};
-    store_mask_record(reinterpret_cast<uint4 *>(deck_ptr(s, i, na) + COG_PD_MASK), bn,
-                      mask_diff_granules(bn, MBits{o1.z, o1.w, o2.x}));
-  }
-  reinterpret_cast<uint2 *>(actions_out + i * COG_ACTION_BYTES)[0] = make_uint2(o2.y, o2.z);
-}
-
-// wbase_in: the wave's first env (k_env_fixup: a parked workgroup's); default blockIdx.x * NL
-template <int SRC, bool FIX, int NL, bool PIPE = false>
-DEV uint32_t rollout_pass(LaneLds<NL> &L, const DevState &s_glob, int steps, uint32_t *__restrict__ rngs_glob,
-                          uint8_t *__restrict__ actions_glob, uint32_t park, OutRing *O = nullptr,
-                          size_t wbase_in = ~(size_t)0) {
-  const int l = threadIdx.x;                               // (the stepping wave: threads 0..NL-1)
-  const size_t wbase = wbase_in != ~(size_t)0 ? wbase_in : (size_t)blockIdx.x * NL;
-  const size_t i0 = wbase + l;
-  // (s, i): the wave's view and the lane's index in it, for every record access; the wave's
-  // generation, its encode and the regenerated-map list take the shard's (s_glob, i_glob)
-  const DevState s = wave_view(s_glob, wbase);
-  const size_t i = (size_t)l;
-  const size_t i_glob = i0 < s_glob.n ? i0 : 0;
-  uint32_t *__restrict__ rngs = rngs_glob + wbase;
-  uint8_t *__restrict__ actions_out = actions_glob + wbase * COG_ACTION_BYTES;
-  int t_first = 0;                                         // fix-up: this lane's first full step
-  bool live = i0 < s_glob.n && (!FIX || park != kParkNone);
-  Snap S;
-  uint32_t srng = 0, out = ~0u;                           // out: end_of_step's output cache
-  auto next_of = [&](int a) { return a + 1 >= (int)(S.g1.x & 0xffu) ? 0 : a + 1; };   // n_players
-  if (live) {
-    load_env(s, i, S);
-    lds_fill_players(L, s, i, l);
-    srng = rngs[i];
-  }
-
-  if (FIX) {                                               // step `park`'s episode end
-    bool enc = false, rs = false;
-    uint32_t agent = 0;
-    if (live && (park & kParkRedo)) {                      // step `park` itself was not run
-      t_first = (int)(park & kParkStep);
-    } else if (live) {
-      t_first = (int)(park & kParkStep) + 1;
-      agent = S.g1.y & 0xffu;
-      const bool finish = (park & kParkFinish) != 0u;
-      rs = end_of_step_a(s, i, !finish, finish, agent, out);
-    }
-    const bool ok = wave_generate(s_glob, i_glob, rs);               // converged: the whole wave generates
-    if (live) {
-      if (rs) enc = end_of_step_b(s_glob, i_glob, ok, agent, out);
-      load_env(s, i, S);                                   // reset: reload from the stored state
-      lds_fill_players(L, s, i, l);
-    }
-    wave_encode(s_glob, i_glob, enc);                                // converged: the whole wave encodes
-  }
-  if (live) {
-    const int ag = (int)(S.g1.y & 0xffu);
-    lds_players(L, l, ag, next_of(ag), S);
-  }
-  // Every load above completes before the loop: the loop issues no load whose wait could be
-  // merged with them, so the wait-count pass places no per-iteration vmcnt wait for registers
-  // they wrote (such a wait, executed every step, would also wait for the step's stores).
-  __builtin_amdgcn_s_waitcnt(0);
-  if (PIPE && !FIX) __syncthreads();                       // the decks in LDS: the storing wave's image
-  PH_DECL;
-  for (int t = 0; t < steps; t++) {
-    if (PIPE) {                                            // every lane, every step: the records
-      if (t) __syncthreads();                              // of step t - 1 to the storing wave
-      if (!live) O->g[t & 1][13][l] = make_uint4(0u, 0u, 0u, 0u);   // (no record)
-    }
-    if (!FIX && !PIPE && !live) break;                     // lean: a parked lane leaves the loop
-    bool enc = false, ended = false, rs = false;
-    uint32_t agent = 0;
-    if (live && t >= t_first) {
-      RegEnv R;
-      regs_env(R, S);
-      R.tab = L.tab;
-      const int ag = (int)R.agent();                       // S holds ag's and na's records: read
-      const int na = ag + 1 >= (int)R.n_players() ? 0 : ag + 1;   // at the end of the last step
-      uint8_t act[5];
-      PH(0);
-      if (SRC == MASK_SELECTED) step_action<SRC>(R, make_uint2(0u, 0u), srng, act);
-      regs_players(R, S);
-      if (SRC == MASK_STORED) step_action<SRC>(R, make_uint2(0u, 0u), srng, act);
-      PH(1);
-      const bool was_done = R.done() != 0u;
-      const bool finish = !was_done && step_regs(R, act, s, i, na PH_PASS);
-      if (finish) R.set_done(1u);
-      PH(2);
-      // the player records to this wave's LDS, and the next step's players back, before the
-      // store phase: the LDS round trip overlaps the stores instead of stalling the loop's tail
-      L.pl[ag][l] = pack_player(R.P);
-      L.cells[ag][l] = R.cells_a;
-      L.heads[ag][l] = mbits_u4(bits_of(R.sta));
-      if (na != ag) L.heads[na][l] = mbits_u4(bits_of(R.stn));
-#pragma unroll
-      for (int k = 0; k < 7; k++) L.deck[ag][k][l] = make_uint4(R.d[4 * k], R.d[4 * k + 1], R.d[4 * k + 2], R.d[4 * k + 3]);
-      agent = R.agent();
-      Snap N;                                              // the next step's player records
-      lds_players(L, l, (int)agent, next_of((int)agent), N);
-      PH(3);
-      if (PIPE) {
-        out_record_write(*O, t & 1, l, ag, na, S, R, act);
-      } else {
-        store_outputs(s, i, ag, na, S, R);
-        store_action(actions_out + i * COG_ACTION_BYTES, act);
-      }
-      PH(4);
-      // the next step's image: registers (env level) and the player records just read
-      S.g0 = make_uint4(R.rng, R.seed, R.max_steps, R.turn_counter);
-      S.g1 = make_uint4(R.g1x, R.g1y, R.in_market, R.flags);
-      S.g2 = R.g2;
-      S.avail = R.avail;
-      S.info_steps = R.info_steps;
-#pragma unroll
-      for (int k = 0; k < 3; k++) S.sh[k] = make_uint4(R.sh[4 * k], R.sh[4 * k + 1], R.sh[4 * k + 2], R.sh[4 * k + 3]);
-      S.sel = bits_of(R.sel);
-      S.pla = N.pla; S.pln = N.pln; S.ca = N.ca; S.cn = N.cn; S.sta = N.sta; S.stn = N.stn;
-#pragma unroll
-      for (int k = 0; k < 7; k++) S.dk[k] = N.dk[k];
-      if (was_done || finish) {                            // episode end: state to HBM first
-        store_private_all(s, i, S, L, l);
-        if (!FIX) {                                        // hand the env to the fix-up pass
-          rngs[i] = srng;
-          park = (uint32_t)t | (finish ? kParkFinish : 0u);
-          live = false;
-          continue;
-        }
-        ended = true;
-        rs = end_of_step_a(s, i, was_done, finish, agent, out);
-      } else {
-        end_of_step_a(s, i, false, false, agent, out);
-      }
-      PH(5);
-    }
-    if (FIX) {                                             // converged: the whole wave generates
-      const bool ok = wave_generate(s_glob, i_glob, rs);
-      if (ended) {
-        if (rs) enc = end_of_step_b(s_glob, i_glob, ok, agent, out);
-        load_env(s, i, S);                                 // reload from the stored state
-        lds_fill_players(L, s, i, l);
-        agent = S.g1.y & 0xffu;
-        lds_players(L, l, (int)agent, next_of((int)agent), S);
-      }
-      wave_encode(s_glob, i_glob, enc);                              // converged: the whole wave encodes
-    }
-    PH(6);
-  }
-  if (PIPE && steps > 0) __syncthreads();                 // the last step's records
-  if (live) {                                              // env-level private state back to HBM
-    store_env_private(s, i, S);                            // (the player records: lds_store_wave)
-    rngs[i] = srng;
-  }
-  if (!FIX) PH_FLUSH(s);
-  return FIX ? kParkNone : park;
-}
-
-template <int SRC, int NL>
-__global__ void __launch_bounds__(NL) k_env_rollout(DevState s, int steps, uint32_t *__restrict__ rngs,
-                                                    uint8_t *__restrict__ actions_out) {
-  __shared__ LaneLds<NL> L;
-  const size_t base = (size_t)blockIdx.x * NL;
-  const int ne = (int)min((size_t)NL, s.n - base);
-  uid_tab_fill(L.tab);
-  const uint32_t park = rollout_pass<SRC, false, NL>(L, s, steps, rngs, actions_out, kParkNone);
-  if (__builtin_amdgcn_ballot_w64(park != kParkNone))    // (wave-uniform)
-    rollout_pass<SRC, true, NL>(L, s, steps, rngs, actions_out, park);
-  __syncthreads();
-  lds_store_wave<LaneLds<NL>, NL>(L, s, base, ne);
-}
-
-// Shards of <= 32,768 envs leave SIMDs idle (one 64-env wave per SIMD at most): each workgroup
-// gets a second wave for its store phase (OutRing above).  Barriers: one at the start, one per
-// step (the stepping wave hands over step t - 1 at the top of step t, the last step after its
-// loop), one when the storing wave's stores have completed, one before the epilogue.  The fix-up
-// pass (episode ends, resets) then runs on the stepping wave alone with the plain store phase,
-// after an L1 invalidate, since it reloads records the storing wave wrote.
-template <int SRC>
-__global__ void __launch_bounds__(128) k_env_rollout_pipe(DevState s, int steps, uint32_t *__restrict__ rngs,
-                                                          uint8_t *__restrict__ actions_out) {
-  __shared__ LaneLds<64> L;
-  __shared__ OutRing O;
-  const size_t base = (size_t)blockIdx.x * 64;
-  const int ne = (int)min((size_t)64, s.n - base);
-  // (roles rotated per workgroup, so that a CU's two workgroups could not put both stepping waves
-  // on one SIMD, measured the same: profiles/r04y_trio_role_rotation.txt)
-  const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform
-  uid_tab_fill(L.tab);
-  uint32_t park = kParkNone;
-  if (role == 0) {
-    park = rollout_pass<SRC, false, 64, true>(L, s, steps, rngs, actions_out, kParkNone, &O);
-    __syncthreads();                                       // the storing wave's stores are done
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");     // (drop L1 lines they replaced)
-    if (__builtin_amdgcn_ballot_w64(park != kParkNone))    // (wave-uniform)
-      rollout_pass<SRC, true, 64>(L, s, steps, rngs, actions_out, park);
-  } else {
-    const int l = (int)threadIdx.x - 64;
-    const DevState v = wave_view(s, base);
-    uint8_t *av = actions_out + base * COG_ACTION_BYTES;
-    DeckImage I;
-    __syncthreads();                                       // the stepping wave's fill is in LDS: the
-    if (l < ne) {                                          // image from there, not a second read of
-#pragma unroll                                             // every deck from memory
-      for (int p = 0; p < 4; p++)
-#pragma unroll
-        for (int k = 0; k < 7; k++) I.d[p][k] = L.deck[p][k][l];
-    }
-    for (int t = 0; t < steps; t++) {
-      __syncthreads();
-      if (l < ne) out_record_store(O, t & 1, l, v, (size_t)l, av, I);
-    }
-    __builtin_amdgcn_s_waitcnt(0);                         // every store of this wave completed
-    __syncthreads();
-  }
-  __syncthreads();
-  if (role == 0) lds_store_wave<LaneLds<64>, 64>(L, s, base, ne);
-}
-
 // ------------------------------------------------------------------------------------------
-// Duo rollout (round 3): two waves per 64-env workgroup -- a stepping wave and a storing wave --
-// sized so that FOUR workgroups share a CU (32,000 B of LDS each, <= 256 VGPRs + AGPRs per
-// work-item), i.e. two waves per SIMD at 65,536 envs.  A lone wave issues at most one
-// instruction per quad-cycle; the SIMD's VALU takes one per two cycles, so the storing wave of
-// one workgroup runs beside the stepping wave of another on the same SIMD, and the stepping wave
-// runs only the game logic.
-//
-// Ownership.  The stepping wave keeps the env in registers (RegEnv, across steps: no per-step
-// image repacking) and every player's counters, neighbourhood cache and stored-mask bits in LDS
-// (`pl`, `cells`, `heads`).  The storing wave keeps every player's DeckObs as last stored
-// (DeckImage, registers) and the "before" images the store phase compares with: the shared
-// block (phase, resources, shop), the selected-mask bits and each player's stored-mask bits.
-// Per step the stepping wave hands over only after-values through a single-buffered LDS ring
-// (`ring`, 14 granules per env), and the storing wave hands back the deck of the player who
-// acts after a turn change (`slot`: the next player's deck as of the step's start -- only the
-// acting player's deck changes within a step).
-//
-// Before the loop, barrier B: the storing wave has loaded every player's deck (its image) and
-// hands the acting player's to the stepping wave through the ring's deck buffer 1, so the stepping
-// wave's prologue is one round of loads (no dependent read of the deck the agent selects).
-// Per step t, two barriers (both waves execute them):
-//   stepping wave: step t on registers; pl/cells/heads of the acting player to LDS;
-//                  X_t; record t to the ring; on a turn change the next player's records from
-//                  LDS and its deck from the slot; Y_t
-//   storing wave:  (X_0 after its prologue) Y_t; record t from the ring into registers; update
-//                  its images; the slot for step t + 1; X_{t+1}; the stores of record t
-// The storing wave reaches X long before the stepping wave ends its step, and the stepping wave
-// reaches Y long after the storing wave's stores were issued, so neither barrier stalls the
-// stepping wave beyond its own issue.
-//
-// Episode ends (and envs that start a launch done) park as in k_env_rollout's lean pass: the
-// lane stores its private state, records its park code in DevState::park and leaves the loop;
-// k_env_fixup, launched right after on the same stream, completes them.  The fix-up's register
-// appetite (map generation, the full step) therefore does not cap this kernel's occupancy.
-constexpr int kRingG = 7, kSlotG = 7;
-struct DuoLds {
-  uint4 pl[4][64];                    // [player][lane]: PlayerPriv (packed)
-  uint2 cells[4][64];                 // neighbourhood caches
-  uint4 heads[4][64];                 // stored-mask bits (MBits + pad)
-  uint4 ring[kRingG][64];             // step record, stepping wave -> storing wave
-  uint4 deckr[2][7][64];              // the record's DeckObs, double-buffered (written before X)
-  uint4 slot[kSlotG][64];             // next player's DeckObs, storing wave -> stepping wave
-  UidEntry tab[kUidTab];
-};
-static_assert(sizeof(DuoLds) <= 40960, "four duo workgroups per CU");
-// step record t: deckr[t & 1] = the acting player's DeckObs after the step, and ring granules
-//   0-2   ObsData 16128..16175 (phase, resources, shop) after the step
-//   3     selected-mask bits; .w = meta (below)
-//   4     the acting player's stored-mask bits; .w = action bytes 0..3
-//   5     the next player's stored-mask bits; .w = action byte 4
-//   6     EnvPriv granule 2 (map bounds + locations), read when the acting player moved
-// meta: bit 0 valid, 1 moved, 2-3 ag, 4-5 na, 6-7 na1 (the player after the next step's
-// acting player), 8-15 Info steps byte of ag, 16 the episode ended (parked: dones / agent are
-// left to the fix-up), 24-31 agent after the step
-constexpr uint32_t kMetaValid = 1u, kMetaMoved = 2u, kMetaEnded = 1u << 16;
-constexpr uint32_t kMetaStepped = 1u << 17;               // (trio) the step ran: the env was not done
-
-DEV uint32_t next_player(uint32_t a, uint32_t np) { return a + 1u >= np ? 0u : a + 1u; }
-
-// The env-level private records of env i from the stepping wave's registers (EnvPriv granules
-// 0, 1, 3, the selected mask's bits).  The player records (counters, neighbourhood caches,
-// stored-mask bits) are stored from the wave's LDS by the epilogue (lds_store_wave), parked envs'
-// included, after the last update of them.  DEFER (the trio): the env rng is the drawing wave's
-// (it stores it at its end), so granule 0's first dword is left alone.
-template <bool DEFER>
-DEV void duo_store_env_private(const DevState &s, size_t i, const RegEnv &R) {
-  uint4 *pw = reinterpret_cast<uint4 *>(s.priv + i);
-  if (DEFER) reinterpret_cast<uint3 *>(reinterpret_cast<uint32_t *>(pw) + 1)[0] = make_uint3(R.seed, R.max_steps, R.turn_counter);
-  else pw[0] = make_uint4(R.rng, R.seed, R.max_steps, R.turn_counter);
-  pw[1] = make_uint4(R.g1x, R.g1y, R.in_market, R.flags);
-  reinterpret_cast<uint32_t *>(pw + 3)[0] = R.info_steps;
-  s.heads[5 * i] = mbits_u4(bits_of(R.sel));
-}
-
-// The deferred turn end (the trio rollout: selected masks, >= 3 players).  The stepping wave ends
-// a turn without touching the deck -- no discard, no draws -- and the drawing wave completes it
-// from the step record (the acting player's deck after the step, its counters in `pl`, the saved
-// mask) with the env rng, which it owns: Player::end_turn's discard + draw (player.cpp:170-180),
-// then the saved mask gains the drawn cards (draw's mask updates, cards.cpp:183-211, precede
-// save_actionmask).  Nothing the stepping wave reads before that player acts again depends on it:
-// with >= 3 players the next two agents are other players, whose turn ends lie at least two steps
-// back.  Any action outside the lean step (lean_player: never in the canonical loop) parks
-// the env with kParkRedo, and k_env_fixup runs that step and the rest with the full step.
-
-template <int SRC>
-DEV void duo_stepper(DuoLds &D, const DevState &s_glob, int steps, uint32_t *__restrict__ rngs_glob) {
-  const int l = threadIdx.x;
-  const size_t wbase = (size_t)blockIdx.x * 64;
-  const DevState s = wave_view(s_glob, wbase);
-  const size_t i = (size_t)l;
-  const int ne = (int)min((size_t)64, s_glob.n - wbase);
-  uint32_t *__restrict__ rngs = rngs_glob + wbase;
-  bool live = l < ne;
-  uint32_t park = kParkNone, srng = 0;
-  RegEnv R;
-  int ag = 0, na = 0;
-  if (live) {
-    Snap S;
-    load_env(s, i, S);
-    regs_env(R, S);
-    const uint4 *pv4 = reinterpret_cast<const uint4 *>(s.priv + i);
-#pragma unroll
-    for (int p = 0; p < 4; p++) {
-      D.pl[p][l] = pv4[4 + p];
-      D.cells[p][l] = reinterpret_cast<const uint2 *>(pv4 + 8)[p];
-      D.heads[p][l] = s.heads[5 * i + 1 + p];
-    }
-    srng = rngs[i];
-    ag = (int)R.agent();
-    na = (int)next_player((uint32_t)ag, R.n_players());
-    R.P = unpack_player(D.pl[ag][l]);
-    R.na_active = (D.pl[na][l].y >> 16) & 0xffu;
-    R.cells_a = D.cells[ag][l];
-    R.cells_n = D.cells[na][l];
-    R.sta = heads_of(mbits_of(D.heads[ag][l]));
-    R.stn = heads_of(mbits_of(D.heads[na][l]));
-  }
-  R.tab = D.tab;
-  // every load above completes before the loop (no per-iteration vmcnt wait covers them)
-  __builtin_amdgcn_s_waitcnt(0);
-  __syncthreads();                                         // B: the storing wave loaded every deck;
-  if (live) {                                              // the acting player's from its hand-over
-#pragma unroll                                             // (no second, dependent read of memory)
-    for (int k = 0; k < 7; k++) {
-      const uint4 v = D.deckr[1][k][l];
-      R.d[4 * k] = v.x; R.d[4 * k + 1] = v.y; R.d[4 * k + 2] = v.z; R.d[4 * k + 3] = v.w;
-    }
-  }
-  PH_DECL;
-  for (int t = 0; t < steps; t++) {
-    bool ended = false, finish = false;
-    uint8_t act[5];
-    if (live) {
-      step_action<SRC>(R, make_uint2(0u, 0u), srng, act);
-      const bool was_done = R.done() != 0u;
-      finish = !was_done && step_regs(R, act, s, i, na PH_PASS);
-      if (finish) R.set_done(1u);
-      ended = was_done || finish;
-      PH(0);
-      D.pl[ag][l] = pack_player(R.P);
-      D.cells[ag][l] = R.cells_a;
-      D.heads[ag][l] = mbits_u4(bits_of(R.sta));
-      if (na != ag) D.heads[na][l] = mbits_u4(bits_of(R.stn));
-#pragma unroll
-      for (int k = 0; k < 7; k++)                          // (buffer t & 1: record t - 2's, taken)
-        D.deckr[t & 1][k][l] = make_uint4(R.d[4 * k], R.d[4 * k + 1], R.d[4 * k + 2], R.d[4 * k + 3]);
-      PH(1);
-    }
-    __syncthreads();                                       // X_t: record t - 1 taken, slot written
-    PH(2);
-    if (live) {
-      const int ag1 = (int)R.agent();
-      const int na1 = (int)next_player((uint32_t)ag1, R.n_players());
-      const MBits bs = bits_of(R.sel), ba = bits_of(R.sta), bn = bits_of(R.stn);
-      const uint32_t info = (R.info_steps >> (8 * ag)) & 0xffu;
-      const uint32_t meta = kMetaValid | (R.moved ? kMetaMoved : 0u) | (uint32_t)ag << 2 | (uint32_t)na << 4 |
-                            (uint32_t)na1 << 6 | info << 8 | (ended ? kMetaEnded : 0u) | (uint32_t)ag1 << 24;
-#pragma unroll
-      for (int k = 0; k < 3; k++) D.ring[k][l] = make_uint4(R.sh[4 * k], R.sh[4 * k + 1], R.sh[4 * k + 2], R.sh[4 * k + 3]);
-      D.ring[3][l] = make_uint4(bs.w0, bs.w1, bs.w2, meta);
-      D.ring[4][l] = make_uint4(ba.w0, ba.w1, ba.w2,
-                                (uint32_t)act[0] | (uint32_t)act[1] << 8 | (uint32_t)act[2] << 16 | (uint32_t)act[3] << 24);
-      D.ring[5][l] = make_uint4(bn.w0, bn.w1, bn.w2, (uint32_t)act[4]);
-      D.ring[6][l] = R.g2;
-      R.moved = false;
-      if (ag1 != ag) {                                     // turn change: ag1 == na acts next
-#pragma unroll
-        for (int k = 0; k < 7; k++) {
-          const uint4 v = D.slot[k][l];
-          R.d[4 * k] = v.x; R.d[4 * k + 1] = v.y; R.d[4 * k + 2] = v.z; R.d[4 * k + 3] = v.w;
-        }
-        R.P = unpack_player(D.pl[ag1][l]);
-        R.cells_a = R.cells_n;
-        R.sta = R.stn;
-        R.stn = heads_of(mbits_of(D.heads[na1][l]));
-        R.cells_n = D.cells[na1][l];
-        R.na_active = (D.pl[na1][l].y >> 16) & 0xffu;
-      }
-      if (ended) {                                         // hand the env to k_env_fixup
-        duo_store_env_private<false>(s, i, R);
-        rngs[i] = srng;
-        park = (uint32_t)t | (finish ? kParkFinish : 0u);
-        live = false;
-      }
-      ag = ag1;
-      na = na1;
-    } else {
-      D.ring[3][l] = make_uint4(0u, 0u, 0u, 0u);           // no record
-    }
-    PH(3);
-    __syncthreads();                                       // Y_t: record t in the ring
-    PH(4);
-  }
-  __syncthreads();                                         // X_steps
-  PH_FLUSH(s_glob);
-  if (live) {                                              // env-level private state back to HBM
-    duo_store_env_private<false>(s, i, R);
-    rngs[i] = srng;
-  }
-  if (l < ne) s.park[i] = park;
-  park_list_push(s_glob, park != kParkNone);
-  lds_store_wave<DuoLds, 64>(D, s, 0, ne);                 // every player's records (cooperative)
-}
-
-DEV uint4 sel4_of(const DeckImage &I, int p, int k) {      // I.d[p][k] for a lane-varying p
-  uint4 v = I.d[3][k];
-#pragma unroll
-  for (int q = 2; q >= 0; q--) v = sel4(p == q, I.d[q][k], v);
-  return v;
-}
-DEV MBits selm(const MBits b[4], int p) {
-  MBits v = b[3];
-#pragma unroll
-  for (int q = 2; q >= 0; q--) {
-    v.w0 = p == q ? b[q].w0 : v.w0;
-    v.w1 = p == q ? b[q].w1 : v.w1;
-    v.w2 = p == q ? b[q].w2 : v.w2;
-  }
-  return v;
-}
-DEV void setm(MBits b[4], int p, const MBits &v) {
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    b[q].w0 = p == q ? v.w0 : b[q].w0;
-    b[q].w1 = p == q ? v.w1 : b[q].w1;
-    b[q].w2 = p == q ? v.w2 : b[q].w2;
-  }
-}
-
-// DEFER: the turn end of record t's acting player ag (meta: ag1 != ag), on the drawing wave --
-// Player::end_turn's discard + draw on the deck as the step left it, with the env rng; the saved
-// mask gains the drawn cards; the player's counters and stored-mask bits go back to the LDS
-// records the stepping wave reads when ag acts again.
-template <class Lds>
-DEV void duo_turn_end(Lds &D, int l, int ag, uint4 dk[7], MBits &ba, uint32_t &rng, uint32_t &flags) {
-  RegEnv E;
-#pragma unroll
-  for (int k = 0; k < 7; k++) {
-    E.d[4 * k] = dk[k].x; E.d[4 * k + 1] = dk[k].y; E.d[4 * k + 2] = dk[k].z; E.d[4 * k + 3] = dk[k].w;
-  }
-  E.P = unpack_player(D.pl[ag][l]);
-  E.rng = rng;
-  E.sel = heads_of(ba);
-  E.flags = 0u;
-  E.tab = D.tab;
-  E.end_turn_deck();
-#pragma unroll
-  for (int k = 0; k < 7; k++) dk[k] = make_uint4(E.d[4 * k], E.d[4 * k + 1], E.d[4 * k + 2], E.d[4 * k + 3]);
-  ba = bits_of(E.sel);
-  rng = E.rng;
-  D.pl[ag][l] = pack_player(E.P);
-  D.heads[ag][l] = mbits_u4(ba);
-  flags |= E.flags;
-}
-
-DEV void duo_storer(DuoLds &D, const DevState &s_glob, int steps, uint8_t *__restrict__ actions_glob) {
-  const int l = (int)threadIdx.x - 64;
-  const size_t wbase = (size_t)blockIdx.x * 64;
-  const DevState s = wave_view(s_glob, wbase);
-  const size_t i = (size_t)l;
-  const bool live = wbase + (size_t)l < s_glob.n;
-  uint8_t *__restrict__ av = actions_glob + wbase * COG_ACTION_BYTES;
-  DeckImage I;
-  uint4 shb[3];
-  MBits selb = {0u, 0u, 0u}, stb[4];
-  uint32_t out = ~0u;                                      // dones[i] | agent_selection[i] << 8 as stored
-  if (live) {
-    deck_image_load(I, s, i);
-    const uint4 *sh4 = reinterpret_cast<const uint4 *>(s.obs + i * COG_OBS_BYTES + COG_OBS_PHASE);
-#pragma unroll
-    for (int k = 0; k < 3; k++) shb[k] = sh4[k];
-    selb = mbits_of(s.heads[5 * i]);
-#pragma unroll
-    for (int p = 0; p < 4; p++) stb[p] = mbits_of(s.heads[5 * i + 1 + p]);
-    const uint4 g1 = reinterpret_cast<const uint4 *>(s.priv + i)[1];
-    const int ag0 = (int)(g1.y & 0xffu), na0 = (int)next_player(g1.y & 0xffu, g1.x & 0xffu);
-#pragma unroll
-    for (int k = 0; k < 7; k++) {
-      D.slot[k][l] = sel4_of(I, na0, k);
-      D.deckr[1][k][l] = sel4_of(I, ag0, k);               // (buffer 1 is first written at step 1)
-    }
-  }
-  __syncthreads();                                         // B: the acting player's deck handed over
-  __syncthreads();                                         // X_0
-  PH_DECL;
-  for (int t = 0; t < steps; t++) {
-    __syncthreads();                                       // Y_t
-    PH(5);
-    uint4 g[kRingG], dk[7];
-#pragma unroll
-    for (int k = 0; k < kRingG; k++) g[k] = D.ring[k][l];
-#pragma unroll
-    for (int k = 0; k < 7; k++) dk[k] = D.deckr[t & 1][k][l];
-    const uint32_t meta = g[3].w;
-    const bool rec = live && (meta & kMetaValid);
-    const int ag = (int)((meta >> 2) & 3u), na = (int)((meta >> 4) & 3u), na1 = (int)((meta >> 6) & 3u);
-    if (rec) {
-      uint32_t dm = 0;                                     // deck granules that changed
-#pragma unroll
-      for (int k = 0; k < 7; k++) {
-        if (ne4(dk[k], sel4_of(I, ag, k))) dm |= 1u << k;
-#pragma unroll
-        for (int p = 0; p < 4; p++) I.d[p][k] = sel4(ag == p, dk[k], I.d[p][k]);
-      }
-#pragma unroll
-      for (int k = 0; k < 7; k++) D.slot[k][l] = sel4_of(I, na1, k);
-      PH(6);
-      uint8_t *ob = s.obs + i * COG_OBS_BYTES;
-      s.info[i * COG_INFO_BYTES + COG_AGENT_INFO0 + COG_AGENT_INFO_STRIDE * ag] = (uint8_t)(meta >> 8);
-      if (meta & kMetaMoved) reinterpret_cast<uint4 *>(s.priv + i)[2] = g[6];
-#pragma unroll
-      for (int k = 0; k < 3; k++) {
-        if (ne4(g[k], shb[k])) reinterpret_cast<uint4 *>(ob + COG_OBS_PHASE)[k] = g[k];
-        shb[k] = g[k];
-      }
-      uint8_t *deck = deck_ptr(s, i, ag);
-#pragma unroll
-      for (int k = 0; k < 7; k++)
-        if ((dm >> k) & 1u) reinterpret_cast<uint4 *>(deck)[k] = dk[k];
-      const MBits bs{g[3].x, g[3].y, g[3].z}, ba{g[4].x, g[4].y, g[4].z};
-      store_mask_record(reinterpret_cast<uint4 *>(s.sel + i * COG_MASK_BYTES), bs, mask_diff_granules(bs, selb));
-      selb = bs;
-      store_mask_record(reinterpret_cast<uint4 *>(deck + COG_PD_MASK), ba, mask_diff_granules(ba, selm(stb, ag)));
-      setm(stb, ag, ba);
-      if (na != ag) {
-        const MBits bn{g[5].x, g[5].y, g[5].z};
-        store_mask_record(reinterpret_cast<uint4 *>(deck_ptr(s, i, na) + COG_PD_MASK), bn,
-                          mask_diff_granules(bn, selm(stb, na)));
-        setm(stb, na, bn);
-      }
-      reinterpret_cast<uint2 *>(av + i * COG_ACTION_BYTES)[0] = make_uint2(g[4].w, g[5].w);
-      if (!(meta & kMetaEnded)) {                          // dones[i] = 0, agent_selection[i]
-        const uint32_t agent = meta >> 24;                 // (an ended episode: k_env_fixup)
-        if (out & 0xffu) s.done[i] = 0;
-        if (((out >> 8) & 0xffu) != agent) s.agent[i] = (uint8_t)agent;
-        out = agent << 8;
-      }
-    }
-    PH(13);
-    __syncthreads();                                       // X_{t+1}
-    PH(7);
-  }
-  PH_FLUSH(s_glob);
-}
-
-template <int SRC>
-__global__ void __launch_bounds__(128) k_env_rollout_duo(DevState s, int steps, uint32_t *__restrict__ rngs,
-                                                         uint8_t *__restrict__ actions_out) {
-  __shared__ DuoLds D;
-  // (roles rotated per workgroup, so that a CU's two workgroups could not put both stepping waves
-  // on one SIMD, measured the same: profiles/r04y_trio_role_rotation.txt)
-  const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // wave-uniform
-  park_list_clear_other(s);
-  uid_tab_fill(D.tab);
-  if (role == 0) {
-    __builtin_amdgcn_s_setprio(3);                         // the stepping wave wins VALU issue on
-                                                           // a SIMD it shares with a storing wave
-    duo_stepper<SRC>(D, s, steps, rngs);
-  } else {
-    duo_storer(D, s, steps, actions_out);
-  }
-}
-
+// The rollouts: parts of their own under engine/, each included where its text stood
 // ------------------------------------------------------------------------------------------
-// Trio rollout (k_env_rollout_trio with its lean image and compact deck): a part of its own
-// ------------------------------------------------------------------------------------------
-#include "engine/rollout_trio.h"
+#include "engine/rollout_wave.h"   // LaneLds, the park list, OutRing, DeckImage, k_env_rollout, k_env_rollout_pipe
+#include "engine/rollout_duo.h"    // the duo rollout
+#include "engine/rollout_trio.h"   // the trio rollout, its lean image and compact deck
 
 // The envs a duo / trio launch parked (episode ends; the trio's actions outside its lean step):
 // for each workgroup on the launch's parked list (park_list_push), one wave runs k_env_rollout's
@@ -3721,12 +2919,60 @@ __global__ void __launch_bounds__(256) k_stream_mix(const u32x4_t *__restrict__ 
 // host launchers
 // ------------------------------------------------------------------------------------------
 static inline unsigned blocks_for(size_t n, unsigned t) { return (unsigned)((n + t - 1) / t); }
+static inline int launched() { return hipGetLastError() == hipSuccess ? 0 : -1; }   // after a launcher's launches
+// `launch` written once for two kernel instances: it names a constant NAME that the macro declares, = A
+// where cond holds, else = B (A's instance first).  BY_MASK_SOURCE declares SRC, the mask source.
+// (variadic: the launch macro's expansion has commas of its own)
+#define LAUNCH_EITHER(cond, NAME, A, B, ...)                                                           \
+  do {                                                                                                 \
+    if (cond) { constexpr auto NAME = A; __VA_ARGS__; } else { constexpr auto NAME = B; __VA_ARGS__; } \
+  } while (0)
+#define BY_MASK_SOURCE(src, ...) LAUNCH_EITHER((src) == MASK_STORED, SRC, MASK_STORED, MASK_SELECTED, __VA_ARGS__)
+
+// The environment switches, read once at first use (a process keeps the values it started with):
+//   $COG_ROLLOUT           rollout    unset, empty or auto: RK_AUTO, rollout_kind's table; duo | wave: that kind
+//                                     (duo: the trio where it applies); anything else: pipe
+//   $COG_TRIO              trio       first character 0: no trio, the duo in its place (A/B); anything else: on
+//   $COG_TRIO_EPW          trio_epw   32 | 64: envs per trio workgroup; anything else: 64
+//   $COG_TRIO_WPC          trio_wpc   1..4: trio workgroups per CU (A/B); anything else: 0, by the grid (trio_pad_lds)
+//   $COG_TRIO_JT           trio_jt    0 / non-zero: the trio's LAT form off / on (A/B); negative or unset: -1, by the grid
+//   $COG_DEBUG_REDO_STEP   redo_step  test hook (DevState::redo_at): the step; unset: -1
+//   $COG_DEBUG_PARK_NOFIX  park_nofix_step, _env   test hook "t:i": parks env i (local index; 0 without ":i") at step t of
+//                                     each launch and keeps a no-fix-up launch so (the guard's test: the park must surface
+//                                     as F_PARK_NOFIX); unset: step -1
+enum RolloutKind : int { RK_AUTO = -1, RK_DUO = 0, RK_WAVE = 1, RK_PIPE = 2, RK_TRIO = 3 };
+struct Switches {
+  int rollout, trio_epw, trio_wpc, trio_jt, redo_step, park_nofix_step;
+  long long park_nofix_env;
+  bool trio;
+};
+static int env_int(const char *e, int unset) { return e && *e ? atoi(e) : unset; }
+static const Switches &switches() {
+  static const Switches sw = [] {
+    Switches w;
+    const char *e = getenv("COG_ROLLOUT");
+    w.rollout = !e || !*e || !strcmp(e, "auto") ? RK_AUTO
+                : !strcmp(e, "duo") ? RK_DUO : !strcmp(e, "wave") ? RK_WAVE : RK_PIPE;
+    e = getenv("COG_TRIO");
+    w.trio = !(e && *e == '0');
+    w.trio_epw = env_int(getenv("COG_TRIO_EPW"), 0) == 32 ? 32 : 64;
+    w.trio_wpc = env_int(getenv("COG_TRIO_WPC"), 0);
+    if (w.trio_wpc < 1 || w.trio_wpc > 4) w.trio_wpc = 0;
+    w.trio_jt = env_int(getenv("COG_TRIO_JT"), -1);
+    w.redo_step = env_int(getenv("COG_DEBUG_REDO_STEP"), -1);
+    e = getenv("COG_DEBUG_PARK_NOFIX");
+    w.park_nofix_step = env_int(e, -1);
+    w.park_nofix_env = e && strchr(e, ':') ? atoll(strchr(e, ':') + 1) : 0;
+    return w;
+  }();
+  return sw;
+}
 
 int launch_init(const DevState &s, const uint32_t *, uint32_t default_seed, void *stream) {
   if (!s.n) return 0;
   hipLaunchKernelGGL(k_init, dim3(blocks_for(s.n, 256)), dim3(256), 0, (hipStream_t)stream, s, default_seed);
   hipLaunchKernelGGL(k_sync_heads, dim3(blocks_for(s.n, 256)), dim3(256), 0, (hipStream_t)stream, s);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launched();
 }
 int launch_reset(const DevState &s, const ResetParams &p, void *stream) {
   if (!s.n) return 0;
@@ -3735,12 +2981,12 @@ int launch_reset(const DevState &s, const ResetParams &p, void *stream) {
   const int epw = (int)(auto_epw < 1 ? 1 : auto_epw > 64 ? 64 : auto_epw);
   hipLaunchKernelGGL(k_reset, dim3(blocks_for(s.n, (unsigned)epw)), dim3(64), 0, (hipStream_t)stream, s, p, epw);
   hipLaunchKernelGGL(k_sync_heads, dim3(blocks_for(s.n, 256)), dim3(256), 0, (hipStream_t)stream, s);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launched();
 }
 int launch_resync(const DevState &s, void *stream) {
   if (!s.n) return 0;
   hipLaunchKernelGGL(k_resync, dim3(blocks_for(s.n, 256)), dim3(256), 0, (hipStream_t)stream, s);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launched();
 }
 int launch_encode_all(const DevState &s, void *stream, int variant) {
   if (!s.n) return 0;
@@ -3751,13 +2997,13 @@ int launch_encode_all(const DevState &s, void *stream, int variant) {
   if (variant == 1) hipLaunchKernelGGL(k_encode_lds<false>, g, b, 0, (hipStream_t)stream, s.cgrid, s.obs, nb);
   else if (variant == 2) hipLaunchKernelGGL(k_encode_direct, g, b, 0, (hipStream_t)stream, s.cgrid, s.obs, nb);
   else hipLaunchKernelGGL(k_encode_lds<true>, g, b, 0, (hipStream_t)stream, s.cgrid, s.obs, nb);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launched();
 }
 int launch_step(const DevState &s, const uint8_t *d_actions, void *stream) {
   if (!s.n) return 0;
   hipLaunchKernelGGL(k_env_step<MASK_EXTERNAL>, dim3(blocks_for(s.n, 64)), dim3(64), 0, (hipStream_t)stream, s,
                      d_actions, nullptr, nullptr);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launched();
 }
 constexpr unsigned kStepPubMaxBlocks = 128;              // (completion counter arrivals)
 bool step_pub_ok(size_t n) { return n && blocks_for(n, 64) <= kStepPubMaxBlocks; }
@@ -3767,46 +3013,35 @@ int launch_step_pub(const DevState &s, const uint8_t *d_actions, void *stream, u
   const SampleSpec none{nullptr, nullptr, nullptr, nullptr, nullptr};
   hipLaunchKernelGGL(k_env_step_pub<MASK_EXTERNAL>, dim3(blocks_for(s.n, 64)), dim3(64), 0, (hipStream_t)stream, s,
                      d_actions, nullptr, nullptr, nullptr, GridSignal{sig_ctr, sig_word, seq}, spec ? *spec : none);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launched();
 }
 int launch_sample_step_pub(const DevState &s, int mask_source, uint32_t *d_rng, uint8_t *d_actions, uint8_t *h_actions,
                            void *stream, uint32_t *sig_ctr, uint32_t *sig_word, uint32_t seq) {
   if (!step_pub_ok(s.n) || !sig_ctr || !s.pub_obs || !s.pub_outs || !s.pub_mir || !h_actions) return -1;
   const dim3 g(blocks_for(s.n, 64)), b(64);
   const SampleSpec none{nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (mask_source == MASK_STORED)
-    hipLaunchKernelGGL(k_env_step_pub<MASK_STORED>, g, b, 0, (hipStream_t)stream, s, nullptr, d_rng, d_actions, h_actions,
-                       GridSignal{sig_ctr, sig_word, seq}, none);
-  else
-    hipLaunchKernelGGL(k_env_step_pub<MASK_SELECTED>, g, b, 0, (hipStream_t)stream, s, nullptr, d_rng, d_actions,
-                       h_actions, GridSignal{sig_ctr, sig_word, seq}, none);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  BY_MASK_SOURCE(mask_source, hipLaunchKernelGGL(k_env_step_pub<SRC>, g, b, 0, (hipStream_t)stream, s, nullptr, d_rng,
+                                                 d_actions, h_actions, GridSignal{sig_ctr, sig_word, seq}, none));
+  return launched();
 }
 int launch_sample(size_t n, const uint8_t *d_masks, uint32_t *d_rng, uint8_t *d_actions, void *stream,
                   uint8_t *h_actions, uint32_t *sig_ctr, uint32_t *sig_word, uint32_t seq) {
   if (!n) return 0;
   hipLaunchKernelGGL(k_sample, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, n, d_masks, d_rng, d_actions,
                      h_actions, GridSignal{sig_ctr, sig_word, seq});
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launched();
 }
 int launch_sample_step(const DevState &s, int mask_source, uint32_t *d_rng, uint8_t *d_actions, void *stream) {
   if (!s.n) return 0;
-  if (mask_source == MASK_STORED)
-    hipLaunchKernelGGL(k_env_step<MASK_STORED>, dim3(blocks_for(s.n, 64)), dim3(64), 0, (hipStream_t)stream, s,
-                       nullptr, d_rng, d_actions);
-  else
-    hipLaunchKernelGGL(k_env_step<MASK_SELECTED>, dim3(blocks_for(s.n, 64)), dim3(64), 0, (hipStream_t)stream, s,
-                       nullptr, d_rng, d_actions);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  BY_MASK_SOURCE(mask_source, hipLaunchKernelGGL(k_env_step<SRC>, dim3(blocks_for(s.n, 64)), dim3(64), 0,
+                                                 (hipStream_t)stream, s, nullptr, d_rng, d_actions));
+  return launched();
 }
 template <int NL>
 static void rollout_launch(const DevState &s, int mask_source, int steps, uint32_t *d_rng, uint8_t *d_actions,
                            hipStream_t st) {
   const dim3 g(blocks_for(s.n, NL)), b(NL);
-  if (mask_source == MASK_STORED)
-    hipLaunchKernelGGL((k_env_rollout<MASK_STORED, NL>), g, b, 0, st, s, steps, d_rng, d_actions);
-  else
-    hipLaunchKernelGGL((k_env_rollout<MASK_SELECTED, NL>), g, b, 0, st, s, steps, d_rng, d_actions);
+  BY_MASK_SOURCE(mask_source, hipLaunchKernelGGL((k_env_rollout<SRC, NL>), g, b, 0, st, s, steps, d_rng, d_actions));
 }
 // Which rollout kernels run a shard of n envs (measured on MI355X, device us/step in 1,000-step
 // launches, profiles/r03_rollout_kinds.txt, profiles/r04e_trio_ab.txt):
@@ -3821,36 +3056,17 @@ static void rollout_launch(const DevState &s, int mask_source, int steps, uint32
 // same cycles per step), and the duo's storing wave costs more work per env-step than its
 // hand-off saves, so the leaner kernels win there.  $COG_ROLLOUT = duo | pipe | wave forces one
 // (duo: the trio where it applies; $COG_TRIO=0 keeps the duo).
-enum RolloutKind : int { RK_AUTO = -1, RK_DUO = 0, RK_WAVE = 1, RK_PIPE = 2, RK_TRIO = 3 };
-static bool trio_on() {                                    // $COG_TRIO=0: no trio (A/B)
-  static const bool on = [] {
-    const char *e = getenv("COG_TRIO");
-    return !(e && *e == '0');
-  }();
-  return on;
-}
-static int rollout_kind(size_t n, int mask_source, bool defer_ok) {
-  static const int forced = [] {
-    const char *e = getenv("COG_ROLLOUT");
-    if (!e || !*e || !strcmp(e, "auto")) return (int)RK_AUTO;
-    return !strcmp(e, "duo") ? (int)RK_DUO : !strcmp(e, "wave") ? (int)RK_WAVE : (int)RK_PIPE;
-  }();
-  const bool trio = defer_ok && mask_source == MASK_SELECTED && trio_on();
+static int rollout_kind(size_t n, int mask_source, bool defer_ok, const Switches &sw) {
+  const int forced = sw.rollout;
+  const bool trio = defer_ok && mask_source == MASK_SELECTED && sw.trio;
   if (forced != RK_AUTO) return forced == RK_DUO && trio ? (int)RK_TRIO : forced;
   if (trio) return RK_TRIO;
   return n <= 16384 ? RK_DUO : n <= 32768 ? RK_PIPE : RK_WAVE;
 }
-int rollout_kind_of(size_t n, int mask_source, bool defer_ok) { return rollout_kind(n, mask_source, defer_ok); }
-// envs per trio workgroup ($COG_TRIO_EPW = 32 | 64 forces it)
-int trio_epw(size_t n) {
-  static const int forced = [] {
-    const char *e = getenv("COG_TRIO_EPW");
-    return e && *e ? atoi(e) : 0;
-  }();
-  if (forced == 32 || forced == 64) return forced;
-  (void)n;
-  return 64;
+int rollout_kind_of(size_t n, int mask_source, bool defer_ok) {
+  return rollout_kind(n, mask_source, defer_ok, switches());
 }
+int trio_epw() { return switches().trio_epw; }            // envs per trio workgroup
 // Trio workgroups per CU.  The compact decks (TrioLds, 53 KB) admit three per CU, but the output
 // stores are bound by each XCD's L2: at 65,536 envs, 32,768 stepping at once keep an XCD's written
 // lines (~4.7 per env-step) within its 4 MiB L2, 49,152 or all 65,536 do not (measured: four per
@@ -3884,12 +3100,8 @@ static CuShape cu_shape() {
 }
 // (*wpc: the workgroups per CU asked for, 0 where none is; the pad is 0 where TrioLds alone leaves no
 // room for one: three and four per CU)
-static size_t trio_pad_lds(unsigned nblocks, const CuShape &c, int *wpc) {
-  static const int forced = [] {
-    const char *e = getenv("COG_TRIO_WPC");
-    return e && *e ? atoi(e) : 0;
-  }();
-  *wpc = forced >= 1 && forced <= 4 ? forced : (nblocks > c.cus ? 2 : 0);
+static size_t trio_pad_lds(unsigned nblocks, const CuShape &c, const Switches &sw, int *wpc) {
+  *wpc = sw.trio_wpc ? sw.trio_wpc : (nblocks > c.cus ? 2 : 0);
   if (!*wpc || c.lds / (size_t)*wpc <= sizeof(TrioLds) + 2048) return 0;
   return c.lds / (size_t)*wpc - 2048 - sizeof(TrioLds);    // (a margin for the allocation granule)
 }
@@ -3899,50 +3111,38 @@ static size_t trio_pad_lds(unsigned nblocks, const CuShape &c, int *wpc) {
 static unsigned fixup_grid(unsigned nblocks, const CuShape &c) { return std::max(1u, std::min(nblocks, c.cus)); }
 // The form of a duo / trio launch over n envs on a device of shape c: what launch_rollout launches
 // and what cog_trio_form_of reports
-static TrioForm trio_form(size_t n, bool trio, const CuShape &c) {
-  static const int jt_env = [] {                           // $COG_TRIO_JT = 0 / 1 overrides (A/B)
-    const char *e = getenv("COG_TRIO_JT");
-    return e && *e ? atoi(e) : -1;
-  }();
+static TrioForm trio_form(size_t n, bool trio, const CuShape &c, const Switches &sw) {
   TrioForm f;
-  f.epw = trio ? trio_epw(n) : 64;
+  f.epw = trio ? sw.trio_epw : 64;
   f.workgroups = blocks_for(n, f.epw);
-  f.lat = jt_env >= 0 ? (jt_env != 0) : (f.workgroups <= c.cus ? 1 : 0);
-  f.pad_lds = trio_pad_lds(f.workgroups, c, &f.wpc);
+  f.lat = sw.trio_jt >= 0 ? (sw.trio_jt != 0) : (f.workgroups <= c.cus ? 1 : 0);
+  f.pad_lds = trio_pad_lds(f.workgroups, c, sw, &f.wpc);
   f.fixup_grid = fixup_grid(f.workgroups, c);
   f.cus = c.cus;
   return f;
 }
-TrioForm trio_form_of(size_t n, int device) { return trio_form(n, true, cu_shape_of(device)); }
+TrioForm trio_form_of(size_t n, int device) { return trio_form(n, true, cu_shape_of(device), switches()); }
 int launch_rollout(const DevState &s, int mask_source, int steps, uint32_t *d_rng, uint8_t *d_actions, void *stream,
                    bool defer_ok, uint32_t *park_seq, bool no_fixup) {
   if (!s.n || steps <= 0) return 0;
-  const int kind = rollout_kind(s.n, mask_source, defer_ok);
+  const Switches &sw = switches();                         // (read once per launch)
+  const int kind = rollout_kind(s.n, mask_source, defer_ok, sw);
   if (kind == RK_DUO || kind == RK_TRIO) {
     if (!park_seq || !s.parkq) return -1;
     const hipStream_t st = (hipStream_t)stream;
-    static const int redo_at = [] {                        // test hook (DevState::redo_at)
-      const char *e = getenv("COG_DEBUG_REDO_STEP");
-      return e && *e ? atoi(e) : -1;
-    }();
-    // test hook: "t:i" parks env i (local index) at step t of each launch and keeps a no-fix-up
-    // launch so (the guard's test: the park must surface as F_PARK_NOFIX)
-    static const std::pair<int, long long> park_nofix = [] {
-      const char *e = getenv("COG_DEBUG_PARK_NOFIX");
-      if (!e || !*e) return std::make_pair(-1, -1LL);
-      const char *c = strchr(e, ':');
-      return std::make_pair(atoi(e), c ? atoll(c + 1) : 0LL);
-    }();
-    DevState sd = s;
-    sd.redo_at = park_nofix.first >= 0 ? park_nofix.first : redo_at;
-    sd.redo_env = park_nofix.first >= 0 ? (int32_t)park_nofix.second : -1;
+    DevState sd = s;                                       // (the two test hooks)
+    sd.redo_at = sw.park_nofix_step >= 0 ? sw.park_nofix_step : sw.redo_step;
+    sd.redo_env = sw.park_nofix_step >= 0 ? (int32_t)sw.park_nofix_env : -1;
     sd.park_par = (*park_seq)++ & 1u;
     // (the redo hook parks every env: never without the fix-up)
-    sd.no_fixup = no_fixup && kind == RK_TRIO && (redo_at < 0 || park_nofix.first >= 0) ? 1u : 0u;
-    const TrioForm f = trio_form(s.n, kind == RK_TRIO, cu_shape());
+    sd.no_fixup = no_fixup && kind == RK_TRIO && (sw.redo_step < 0 || sw.park_nofix_step >= 0) ? 1u : 0u;
+    const TrioForm f = trio_form(s.n, kind == RK_TRIO, cu_shape(), sw);
     const int epw = f.epw;
     const dim3 g(f.workgroups), gf(f.fixup_grid);
     sd.trio_jt = (uint32_t)f.lat;
+    // (These three branches stay written out: the compiler lays the kernel templates' instances out in the
+    // order this file first names them, and one fix-up launch per mask source after the branches names them
+    // in another -- other addresses, worth 1-2 % of the trio's step time: profiles/r06_compact_decks_ab.txt.)
     if (mask_source == MASK_STORED) {
       hipLaunchKernelGGL((k_env_rollout_duo<MASK_STORED>), g, dim3(128), 0, st, sd, steps, d_rng, d_actions);
       hipLaunchKernelGGL((k_env_fixup<MASK_STORED>), gf, dim3(64), 0, st, sd, steps, d_rng, d_actions, epw);
@@ -3950,19 +3150,15 @@ int launch_rollout(const DevState &s, int mask_source, int steps, uint32_t *d_rn
       // (k_env_fixup inside the trio launch, for shards of one workgroup per CU -- inlined, or as a
       // never-inlined call -- was slower: 20-step launch at 8,192 44.2 / 42.0 against 41.3 us,
       // profiles/r04t_trio_fused.txt)
-      if (sd.trio_jt)
-        hipLaunchKernelGGL((k_env_rollout_trio<MASK_SELECTED, true>), g, dim3(256), f.pad_lds, st, sd, steps, epw,
-                           d_rng, d_actions);
-      else
-        hipLaunchKernelGGL((k_env_rollout_trio<MASK_SELECTED, false>), g, dim3(256), f.pad_lds, st, sd, steps, epw,
-                           d_rng, d_actions);
+      LAUNCH_EITHER(sd.trio_jt, LAT, true, false, hipLaunchKernelGGL((k_env_rollout_trio<MASK_SELECTED, LAT>), g, dim3(256),
+                                                                     f.pad_lds, st, sd, steps, epw, d_rng, d_actions));
       if (!sd.no_fixup)
         hipLaunchKernelGGL((k_env_fixup<MASK_SELECTED>), gf, dim3(64), 0, st, sd, steps, d_rng, d_actions, epw);
     } else {
       hipLaunchKernelGGL((k_env_rollout_duo<MASK_SELECTED>), g, dim3(128), 0, st, sd, steps, d_rng, d_actions);
       hipLaunchKernelGGL((k_env_fixup<MASK_SELECTED>), gf, dim3(64), 0, st, sd, steps, d_rng, d_actions, epw);
     }
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return launched();
   }
   // one 64-env wave per workgroup: 32-env workgroups measured 7.3 us/step against 3.8 at 65,536
   // envs (round 2).  The kernel's register allocation (about 490 VGPRs + AGPRs per work-item)
@@ -3970,14 +3166,11 @@ int launch_rollout(const DevState &s, int mask_source, int steps, uint32_t *d_rn
   const hipStream_t st = (hipStream_t)stream;
   if (kind == RK_PIPE) {                                   // SIMDs to spare: the two-wave form
     const dim3 g(blocks_for(s.n, 64)), b(128);
-    if (mask_source == MASK_STORED)
-      hipLaunchKernelGGL((k_env_rollout_pipe<MASK_STORED>), g, b, 0, st, s, steps, d_rng, d_actions);
-    else
-      hipLaunchKernelGGL((k_env_rollout_pipe<MASK_SELECTED>), g, b, 0, st, s, steps, d_rng, d_actions);
+    BY_MASK_SOURCE(mask_source, hipLaunchKernelGGL((k_env_rollout_pipe<SRC>), g, b, 0, st, s, steps, d_rng, d_actions));
   } else {
     rollout_launch<64>(s, mask_source, steps, d_rng, d_actions, st);
   }
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launched();
 }
 // work-items: granule pairs (a workgroup covers 512 consecutive granules), then one per action
 static unsigned publish_blocks(size_t n, size_t outs_bytes, bool actions) {
@@ -3996,7 +3189,7 @@ int launch_publish(const DevState &s, const uint8_t *outs, uint8_t *mir, uint8_t
                      reinterpret_cast<uint4 *>(mir), reinterpret_cast<uint4 *>(h_obs), reinterpret_cast<uint4 *>(h_outs),
                      s.n, outs_g, force, reinterpret_cast<const uint2 *>(d_actions), reinterpret_cast<uint2 *>(h_actions),
                      GridSignal{sig_ctr, sig_word, seq});
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launched();
 }
 bool publish_can_signal(size_t n, size_t outs_bytes, bool actions) {
   return publish_blocks(n, outs_bytes, actions) <= kPublishSignalBlocks;
@@ -4006,38 +3199,31 @@ int launch_copy_peak(const void *src, void *dst, size_t bytes, void *stream, int
   const u32x4_t *a = static_cast<const u32x4_t *>(src);
   u32x4_t *b = static_cast<u32x4_t *>(dst);
   const size_t n16 = bytes / 16;
+  const hipStream_t st = (hipStream_t)stream;
   if (variant & 8) {                                  // the encode's mix: bytes / 16 granules read, 7x written
     const dim3 g(blocks_for(n16, 256)), t(256);
-    if (variant & 1) hipLaunchKernelGGL(k_stream_mix<true>, g, t, 0, (hipStream_t)stream, a, b, n16);
-    else hipLaunchKernelGGL(k_stream_mix<false>, g, t, 0, (hipStream_t)stream, a, b, n16);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-  }
-  if (variant & 16) {                                 // one granule per work-item
+    LAUNCH_EITHER(variant & 1, NT, true, false, hipLaunchKernelGGL(k_stream_mix<NT>, g, t, 0, st, a, b, n16));
+  } else if (variant & 16) {                          // one granule per work-item
     const dim3 g(blocks_for(n16, 256)), t(256);
-    if (variant & 1) hipLaunchKernelGGL(k_copy_one<true>, g, t, 0, (hipStream_t)stream, a, b, n16);
-    else hipLaunchKernelGGL(k_copy_one<false>, g, t, 0, (hipStream_t)stream, a, b, n16);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-  }
-  if (variant & 4) {                                  // one pass, 32 KiB per workgroup
+    LAUNCH_EITHER(variant & 1, NT, true, false, hipLaunchKernelGGL(k_copy_one<NT>, g, t, 0, st, a, b, n16));
+  } else if (variant & 4) {                           // one pass, 32 KiB per workgroup
     const dim3 g(blocks_for(n16, 2048)), t(256);
-    if (variant & 1) hipLaunchKernelGGL(k_copy_block<true>, g, t, 0, (hipStream_t)stream, a, b, n16);
-    else hipLaunchKernelGGL(k_copy_block<false>, g, t, 0, (hipStream_t)stream, a, b, n16);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    LAUNCH_EITHER(variant & 1, NT, true, false, hipLaunchKernelGGL(k_copy_block<NT>, g, t, 0, st, a, b, n16));
+  } else {
+    const dim3 g(variant & 2 ? 8192 : 2048), t(256);  // grid stride: 8 or 32 waves per CU
+    LAUNCH_EITHER(variant & 1, NT, true, false, hipLaunchKernelGGL(k_copy_peak<NT>, g, t, 0, st, a, b, n16));
   }
-  const dim3 g(variant & 2 ? 8192 : 2048), t(256);   // grid stride: 8 or 32 waves per CU
-  if (variant & 1) hipLaunchKernelGGL(k_copy_peak<true>, g, t, 0, (hipStream_t)stream, a, b, n16);
-  else hipLaunchKernelGGL(k_copy_peak<false>, g, t, 0, (hipStream_t)stream, a, b, n16);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launched();
 }
 int launch_signal(uint32_t *d_word, uint32_t seq, void *stream) {
   hipLaunchKernelGGL(k_signal, dim3(1), dim3(64), 0, (hipStream_t)stream, d_word, seq);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launched();
 }
 int launch_seed_sampler(size_t n, uint64_t seed, size_t first, uint32_t *d_rng, void *stream) {
   if (!n) return 0;
   hipLaunchKernelGGL(k_seed_sampler, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, n, seed, first,
                      d_rng);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return launched();
 }
 
 }  // namespace cog

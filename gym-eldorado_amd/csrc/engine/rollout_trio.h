@@ -3,8 +3,9 @@
 // A part of cog_engine.hip, included there inside namespace cog where this text used to stand; not
 // meant to be compiled or included alone.  Needs, defined before it in cog_engine.hip: the PH / STAMP
 // macros, Heads / MBits and the sampler, RegEnv and the card tables of the register-resident step,
-// Snap / deck_ptr / store_mask_record of the lane drivers, the park codes and list, DeckImage, and the
-// duo's meta bits and store helpers.  k_env_fixup and the host launchers after it use its compact deck.
+// Snap / deck_ptr / store_mask_record of the lane drivers; from engine/rollout_wave.h the park codes and
+// list and DeckImage; from engine/rollout_duo.h the duo's meta bits and store helpers.  k_env_fixup and
+// the host launchers after it use its compact deck.
 // ------------------------------------------------------------------------------------------
 // Trio rollout (round 4): the selected-mask loop with >= 3 players at every shard size (cog_rollout_kind),
 // one step's work spread over four waves per 64 envs.  The stepping wave runs the lean step
