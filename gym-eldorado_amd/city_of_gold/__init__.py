@@ -22,6 +22,9 @@ actions and the entropy under new logits, with gradients (a torch.autograd.Funct
 kernels), and mask_records(envs, source) copies the masks a trainer has to record with them.
 turn_gae(values, agents, rewards, dones, last_values) turns a recorded window into per-seat
 advantages and returns (GAE over each seat's own rows of each episode), one HIP kernel.
+policy_features(envs, radius) gives the network's input: a flat (n, 208) tensor and an
+(n, 10, W, W) window of the map centred on the seat's own cell, seen from the acting seat (or any
+seat), positions included, float32 or bfloat16, one HIP kernel between the step and the network.
 
 All computation runs in libcog_hip.so on a gfx950 GPU.  There is no CPU fallback: creating an
 environment without a usable device raises RuntimeError.
@@ -257,6 +260,89 @@ def mask_records(envs, source="selected"):
         return obs.gather(1, cols)
 
 
+FEATURES_VEC, FEATURES_CHANNELS, FEATURES_MAX_RADIUS = 208, 10, 24
+
+
+def policy_features(envs, radius=4, *, seat=None, dtype=None, out=None, stream=None):
+    """A network's input for every env, seen from one seat: (vec, local), two tensors written by one
+    HIP kernel.  The envs' records and views are not touched.
+
+    envs: a single-shard vec env.  radius: an int in [0, 24]; W = 2 radius + 1.  dtype:
+    torch.bfloat16 (the default) or torch.float32, for both tensors.  seat: None, the acting seat
+    (agent_selection & 3, read on the device); an int 0..3, that seat for every env; or an (n,) uint8
+    tensor on the envs' device, one seat per env (its low two bits).  out: None for new tensors, or a
+    pair (vec, local) of contiguous tensors of exactly those shapes, that dtype and that device,
+    aligned to their element only (slices buf_vec[t], buf_loc[t] of a time-major rollout buffer
+    qualify): written in place and returned.
+
+    With s the seat, np the env's n_players, player p's cell (ix_p, iy_p) = (locx - minx + 1,
+    locy - miny + 1), the [ix][iy] index of observations.shared.map, and relative seat r = 1..3 the
+    player (s + r) mod np when r < np, else absent:
+      vec (n, 208), every value as a number (a byte b is float(b), no scaling):
+        0 shared.phase; 1..3 shared.current_resources -- the ACTING player's, whatever `seat` says;
+        4..21 shared.shop; 22 np; 23, 24 own ix, iy; 25..129 the seat's own DeckObs bytes (draw,
+        hand, active, played, discard, 21 types each); 130 + 26 (r - 1) + k for r = 1..3: k = 0
+        present, k = 1, 2 ix_r - ix_own, iy_r - iy_own, k = 3 cards in hand, k = 4 cards in draw,
+        k = 5..25 per card type the total over the five piles (which pile a card lies in is not
+        public); all 26 are 0 for an absent seat.
+      local (n, 10, W, W), channel first: entry [c, a, b] is about the map cell (ix_own - radius + a,
+        iy_own - radius + b): c = 0..5 map features 1..6 of the cell (shared.map[ix, iy, 1 + c]),
+        c = 6, 7, 8: 1 where relative seat 1, 2, 3 stands (players can share a cell), c = 9: 1 where
+        the cell lies inside the 48 x 48 grid; a cell outside it has 0 in all ten channels.
+    An env with s >= np gets all-zero rows.  float32 values are exact; bfloat16 ones are their round
+    to nearest even.  An env whose last reset failed gets unspecified rows.
+
+    The kernel runs on `stream` (default: torch's current stream on the envs' device; -1: the envs'
+    own stream) after the envs' queued work, and the envs' later work (the next step overwrites the
+    records) runs after it.  Nothing waits on the host.  n == 0 launches nothing."""
+    import torch
+    who = "policy_features"
+    if dtype is None:
+        dtype = torch.bfloat16
+    if envs.num_shards != 1:
+        raise ValueError(f"{who} of a {envs.num_shards}-shard env: it needs a single-shard env (one device)")
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 0 <= radius <= FEATURES_MAX_RADIUS:
+        raise ValueError(f"{who}: radius {radius!r} is not an int in [0, {FEATURES_MAX_RADIUS}]")
+    if str(dtype) not in _LOGITS_DTYPES:
+        raise ValueError(f"{who}: dtype {dtype} is neither torch.float32 nor torch.bfloat16")
+    n, dev = envs.num_envs, envs.shard_info(0)[2]
+    device = torch.device("cuda", dev)
+    w = 2 * radius + 1
+    shapes = ((n, FEATURES_VEC), (n, FEATURES_CHANNELS, w, w))
+    mode, seat_int, d_seats = 0, 0, 0
+    if isinstance(seat, torch.Tensor):
+        if seat.device != device or seat.dtype != torch.uint8 or tuple(seat.shape) != (n,) or not seat.is_contiguous():
+            raise ValueError(f"{who}: a seats tensor must be a contiguous ({n},) uint8 tensor on {device}, not "
+                             f"{tuple(seat.shape)} {seat.dtype} on {seat.device}")
+        mode, d_seats = 2, seat.data_ptr()
+    elif seat is not None:
+        if isinstance(seat, bool) or not isinstance(seat, int) or not 0 <= seat <= 3:
+            raise ValueError(f"{who}: seat {seat!r} is not None, an int in 0..3 or an (n,) uint8 tensor")
+        mode, seat_int = 1, seat
+    if out is None:
+        out = tuple(torch.empty(s, dtype=dtype, device=device) for s in shapes)
+    else:
+        if not isinstance(out, (tuple, list)) or len(out) != 2 or not all(isinstance(t, torch.Tensor) for t in out):
+            raise ValueError(f"{who}: out must be a pair (vec, local) of torch tensors")
+        out = tuple(out)
+        for name, t, shape in zip(("vec", "local"), out, shapes):
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{who}: out {name} has shape {tuple(t.shape)}, expected {shape}")
+            if t.dtype != dtype:
+                raise ValueError(f"{who}: out {name} has dtype {t.dtype}, expected {dtype}")
+            if t.device != device:
+                raise ValueError(f"{who}: out {name} is on device {t.device}, the envs are on {device}")
+            if not t.is_contiguous():
+                raise ValueError(f"{who}: out {name} strides {tuple(t.stride())}: it must be contiguous")
+    if n == 0:
+        return out
+    if stream is None:
+        stream = stream_handle(dev)
+    _C.VecEnvBase.policy_features_raw(envs, radius, _LOGITS_DTYPES[str(dtype)], mode, seat_int, d_seats,
+                                      out[0].data_ptr(), out[1].data_ptr(), -1 if stream is None else int(stream))
+    return out
+
+
 _policy_evaluate_fn = None
 _LOGITS_DTYPES = {"torch.float32": 0, "torch.bfloat16": 1}
 
@@ -444,4 +530,4 @@ del _n, _m
 __all__ = ["vec", "Difficulty", "EASY", "MEDIUM", "HARD", "ObsData", "ActionMask", "ActionData", "Info",
            "DeckObs", "SharedObservation", "PlayerData", "PlayerObservation", "action_sampler", "get_vec_env",
            "get_vec_sampler", "get_runner", "device_count", "device_tensors", "stream_handle", "cog_env", "policy_evaluate",
-           "mask_records", "turn_gae"]
+           "mask_records", "turn_gae", "policy_features"]

@@ -1517,6 +1517,57 @@ int cog_policy_gae(const cog_gae_args *a) {
   return COG_OK;
 }
 
+// Seat-relative observation tensors (cog_policy.hip k_policy_features): one kernel on the caller's
+// stream, between the env's queued work (which wrote the records it reads) and the env's later work
+// (which overwrites them), ordered by events as cog_sampler_sample_policy orders its kernel.  It
+// reads engine state and writes the caller's tensors alone: no version, cdeck_ok or host-view state
+// changes.
+int cog_env_policy_features(cog_env *env, const cog_features_args *a) {
+  auto bad = [&](const std::string &msg) { return fail(COG_ERR_INVALID, "policy_features: " + msg); };
+  if (!env || !a) return fail(COG_ERR_INVALID, "NULL argument");
+  if (!single(env)) return bad("it needs a single-shard env (one device)");
+  if (a->radius < 0 || a->radius > COG_FEATURES_MAX_RADIUS)
+    return bad("radius " + std::to_string(a->radius) + " is not in [0, 24]");
+  if (a->dtype != COG_LOGITS_F32 && a->dtype != COG_LOGITS_BF16) return bad("unknown dtype " + std::to_string(a->dtype));
+  if (a->seat_mode != COG_SEAT_ACTING && a->seat_mode != COG_SEAT_FIXED && a->seat_mode != COG_SEAT_POINTER)
+    return bad("unknown seat mode " + std::to_string(a->seat_mode));
+  if (a->seat_mode == COG_SEAT_FIXED && (a->seat < 0 || a->seat > 3))
+    return bad("seat " + std::to_string(a->seat) + " is not in 0..3");
+  if (!env->n) return COG_OK;
+  if (a->seat_mode == COG_SEAT_POINTER && !a->d_seats) return bad("seats pointer is NULL");
+  if (!a->d_vec || !a->d_local) return bad("output pointer is NULL");
+  const uintptr_t esz = a->dtype == COG_LOGITS_BF16 ? 2 : 4;
+  if (reinterpret_cast<uintptr_t>(a->d_vec) % esz || reinterpret_cast<uintptr_t>(a->d_local) % esz)
+    return bad("output pointer is not aligned to its element size");
+  EnvShard &k = env->sh[0];
+  if (k.n > (size_t)0x7fffffffu) return bad("n " + std::to_string(k.n) + " is more than one launch covers");
+  cog::PolicyFeatures p{};
+  p.n = k.n;
+  p.obs = k.s.obs;
+  p.priv = k.s.priv;
+  p.agent = k.s.agent;
+  p.cgrid = k.s.cgrid;
+  p.seats = a->seat_mode == COG_SEAT_POINTER ? a->d_seats : nullptr;
+  p.seat = a->seat_mode == COG_SEAT_FIXED ? a->seat : -1;
+  p.radius = a->radius;
+  p.bf16 = a->dtype == COG_LOGITS_BF16;
+  p.vec = a->d_vec;
+  p.local = a->d_local;
+  DeviceGuard g(k.device);
+  hipStream_t st = a->stream == COG_NO_STREAM ? k.stream : static_cast<hipStream_t>(a->stream);
+  if (st != k.stream) {                                    // after the env's queued work (its records)
+    HIPCHK(hipEventRecord(k.ev, k.stream));
+    HIPCHK(hipStreamWaitEvent(st, k.ev, 0));
+  }
+  if (cog::launch_policy_features(p, st))
+    return fail(COG_ERR_HIP, std::string("policy features launch failed: ") + hipGetErrorString(hipGetLastError()));
+  if (st != k.stream) {                                    // the env's later work (the next step) after it
+    HIPCHK(hipEventRecord(k.ev, st));
+    HIPCHK(hipStreamWaitEvent(k.stream, k.ev, 0));
+  }
+  return COG_OK;
+}
+
 int cog_sampler_sample(cog_sampler *s, const cog_action_mask_t *masks, size_t n) {
   if (!s || (!masks && n)) return fail(COG_ERR_INVALID, "NULL argument");
   if (n != s->n) return fail(COG_ERR_INVALID, "action_mask length != num_envs");

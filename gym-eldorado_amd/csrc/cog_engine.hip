@@ -634,13 +634,7 @@ DEV void finish_episode(const Ctx &e) {
 // ------------------------------------------------------------------------------------------
 // map-observation encode (map.cpp:389-405): feature 0 stays 0 (Q2), f[req+1] = n, f[6] = is_end
 // ------------------------------------------------------------------------------------------
-// Feature f of a hex code, f known at compile time after unrolling.  Code 0 (no hex) and NULL
-// hexes (mountain / start, requirement 5) give all-zero features, like finalize's zero fill.
-DEV uint32_t feat(uint32_t code, int f) {
-  if (f == 0) return 0u;                                   // occupying player: never written (Q2)
-  if (f == 6) return (code >> 6) & 1u;                     // is_end
-  return (((code >> 3) & 7u) == (uint32_t)(f - 1)) ? (code & 7u) : 0u;
-}
+#include "cog_feat.h"   // feat(code, f): feature f of a hex code
 
 // One 16-cell block k (cells 16k..16k+15 of the 48x48 grid, row-major [ix][iy] like the
 // observation) -> output bytes [112k, 112k+112) of the 16,128-byte map: one aligned 16-byte

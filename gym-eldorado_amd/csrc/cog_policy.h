@@ -1,8 +1,9 @@
 // cog_policy.h -- internal interface between the C-ABI layer (cog_abi.cpp) and the policy sampler
 // kernels (cog_policy.hip): masked categorical actions from a batch of logits, and the evaluator of
-// recorded actions under new logits with its gradient, and the per-seat advantage estimator.  Not
-// part of the public ABI (include/cog.h cog_sampler_sample_policy, cog_policy_evaluate,
-// cog_policy_evaluate_backward and cog_policy_gae are).
+// recorded actions under new logits with its gradient, the per-seat advantage estimator, and the
+// seat-relative observation tensors a network takes.  Not part of the public ABI (include/cog.h
+// cog_sampler_sample_policy, cog_policy_evaluate, cog_policy_evaluate_backward, cog_policy_gae and
+// cog_env_policy_features are).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -64,5 +65,27 @@ struct TurnGae {
 
 // 0, or -1 when the launch failed; T == 0 or n == 0 launches nothing
 int launch_turn_gae(const TurnGae &p, void *stream);
+
+// seat-relative observation tensors of a shard's envs (include/cog.h cog_env_policy_features)
+constexpr int kFeatVec = 208;        // flat features per env
+constexpr int kFeatChannels = 10;    // channels of the local map window
+constexpr int kFeatMaxRadius = 24;
+struct EnvPriv;
+struct PolicyFeatures {
+  size_t n;                          // envs
+  const uint8_t *obs;                // DevState::obs: [n] ObsData records (read from byte 16128 on)
+  const EnvPriv *priv;               // DevState::priv
+  const uint8_t *agent;              // DevState::agent
+  const uint8_t *cgrid;              // DevState::cgrid: [n] x 2304 hex codes
+  const uint8_t *seats;              // [n] seat bytes (low two bits), or null: `seat`
+  int seat;                          // 0..3 for every env, or -1: the acting seat (agent)
+  int radius;                        // 0..24: the window is (2 radius + 1)^2 cells
+  int bf16;                          // 0: float32, 1: bfloat16
+  void *vec;                         // [n][208] contiguous, aligned to the element size
+  void *local;                       // [n][10][W][W] contiguous, aligned to the element size
+};
+
+// 0, or -1 when the launch failed; n == 0 launches nothing
+int launch_policy_features(const PolicyFeatures &p, void *stream);
 
 }  // namespace cog

@@ -533,6 +533,23 @@ PYBIND11_MODULE(_city_of_gold, m) {
         // after the work queued on `stream` (-1: no ordering)
         check(cog_env_invalidate_device(e.handle(), stream < 0 ? COG_NO_STREAM : reinterpret_cast<void *>((uintptr_t)stream)));
       }, "stream"_a = -1)
+      .def("policy_features_raw", [](VecEnv &e, int radius, int dtype, int seat_mode, int seat, uintptr_t d_seats,
+                                     uintptr_t d_vec, uintptr_t d_local, int64_t stream) {
+        // cog_env_policy_features over raw device pointers (city_of_gold policy_features is the torch
+        // face): dtype 0 float32 / 1 bfloat16, seat_mode 0 acting / 1 seat / 2 d_seats, stream a
+        // hipStream_t handle (0 = the null stream; -1: the env's own)
+        cog_features_args a{};
+        a.radius = radius;
+        a.dtype = dtype;
+        a.seat_mode = seat_mode;
+        a.seat = seat;
+        a.d_seats = reinterpret_cast<const uint8_t *>(d_seats);
+        a.d_vec = reinterpret_cast<void *>(d_vec);
+        a.d_local = reinterpret_cast<void *>(d_local);
+        a.stream = stream < 0 ? COG_NO_STREAM : reinterpret_cast<void *>((uintptr_t)stream);
+        check(cog_env_policy_features(e.handle(), &a));
+      }, "radius"_a, "dtype"_a, "seat_mode"_a = 0, "seat"_a = 0, "d_seats"_a = 0, "d_vec"_a = 0, "d_local"_a = 0,
+         "stream"_a = -1)
       .def("set_autoreset", [](VecEnv &e, bool on) { check(cog_env_set_autoreset(e.handle(), on ? 1 : 0)); }, "on"_a)
       .def("stream", [](VecEnv &e, int k) { return (uintptr_t)cog_env_shard_stream(e.handle(), k); }, "shard"_a = 0)
       .def("hazards", [](VecEnv &e) {

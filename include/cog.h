@@ -327,6 +327,47 @@ typedef struct cog_gae_args {
   int device; void *stream;                                /* device ordinal; caller's hipStream_t (NULL: the null stream) */
 } cog_gae_args;
 COG_API int cog_policy_gae(const cog_gae_args *a);
+/* Policy features (an addition): a network's input for every env of a single-shard handle, seen
+ * from one seat, as two tensors in device memory written by one kernel.  The engine's records and
+ * views are not touched.  With s the seat (its low two bits), np the env's n_players, player p's
+ * cell (ix_p, iy_p) = (locx[p] - minx + 1, locy[p] - miny + 1), the [ix][iy] index of
+ * observations.shared.map, and relative seat r = 1..3 the player (s + r) mod np when r < np, else
+ * absent:
+ *   vec[i][208], each value as a number (a byte b is float(b), no scaling):
+ *     0 shared.phase; 1..3 shared.current_resources (the ACTING player's, whatever the seat);
+ *     4..21 shared.shop; 22 np; 23, 24 own ix, iy; 25..129 the seat's own DeckObs bytes 0..104
+ *     (draw, hand, active, played, discard: 21 types each); 130 + 26 (r - 1) + k for r = 1..3:
+ *     k = 0 present (1 / 0), k = 1, 2 ix_r - ix_own, iy_r - iy_own, k = 3 cards in hand (sum of
+ *     hand[0..20]), k = 4 cards in draw, k = 5..25 per card type the total over the five piles; all
+ *     26 are 0 for an absent seat.
+ *   local[i][10][W][W], W = 2 radius + 1: entry [c][a][b] is about the map cell
+ *     (ix_own - radius + a, iy_own - radius + b): c = 0..5 map features 1..6 of the cell (what
+ *     shared.map[ix][iy][1 + c] holds, taken from the engine's compact hex codes), c = 6, 7, 8: 1
+ *     where relative seat 1, 2, 3 stands (players can share a cell: the channels are independent),
+ *     c = 9: 1 where the cell lies inside the 48 x 48 grid; a cell outside it has 0 in all ten.
+ * For an env with s >= np both rows are all zeros.  Sums are formed as integers; float32 values are
+ * exact, bfloat16 ones their round to nearest even.  An env whose last reset failed
+ * (COG_HAZ_MAPGEN_FAIL, COG_HAZ_GRID_OVER) gets unspecified rows; nothing outside its own records
+ * is read.
+ * seat_mode COG_SEAT_ACTING: s = agent_selection, read on the device; COG_SEAT_FIXED: s = seat
+ * (0..3) for every env; COG_SEAT_POINTER: s = d_seats[i], n bytes in device memory.  radius 0..24;
+ * dtype COG_LOGITS_F32 / COG_LOGITS_BF16, for both tensors; d_vec, d_local contiguous, aligned to
+ * the element size (any element of a larger buffer may be the first).  The kernel runs on `stream`
+ * (COG_NO_STREAM: the env's own) after the env's queued work, and the env's later work runs after
+ * it; the call does not wait on the host.  n == 0 launches nothing. */
+#define COG_SEAT_ACTING 0
+#define COG_SEAT_FIXED 1
+#define COG_SEAT_POINTER 2
+#define COG_FEATURES_VEC 208
+#define COG_FEATURES_CHANNELS 10
+#define COG_FEATURES_MAX_RADIUS 24
+typedef struct cog_features_args {
+  int radius; int dtype;                                   /* 0..24; COG_LOGITS_F32 / COG_LOGITS_BF16 */
+  int seat_mode; int seat; const uint8_t *d_seats;         /* COG_SEAT_*; FIXED: seat; POINTER: d_seats */
+  void *d_vec; void *d_local;                              /* n x 208 and n x 10 x W x W elements     */
+  void *stream;                                            /* caller's hipStream_t, or COG_NO_STREAM  */
+} cog_features_args;
+COG_API int cog_env_policy_features(cog_env *env, const cog_features_args *a);
 COG_API cog_action_t *cog_sampler_actions(cog_sampler *s);   /* persistent host view */
 COG_API void *cog_sampler_device_actions(cog_sampler *s);    /* device view (shard 0) */
 COG_API void *cog_sampler_shard_device_actions(cog_sampler *s, int shard);
