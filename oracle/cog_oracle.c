@@ -47,7 +47,10 @@ static inline uint32_t mr_next(uint32_t *x) {
 }
 /* uniform_int_distribution<size_t>(a, b) with the "downscaling" branch
  * (urng range 2147483645 > b - a).  Every call consumes >= 1 draw. */
-static uint64_t uid(uint32_t *x, uint64_t a, uint64_t b) {
+/* census (orc_census, orc_sampler_census): cen, when not NULL, points at the two counters
+ * {accepted, rejected} of the calling site; a draw within 31 of the top of the urng's range (the only
+ * draws any range of this game can reject) is counted there.  The counters decide nothing. */
+static uint64_t uid(uint32_t *x, uint64_t a, uint64_t b, uint32_t *cen) {
   const uint64_t urngrange = 2147483645ull;
   const uint64_t urange = b - a;
   uint64_t ret;
@@ -57,6 +60,7 @@ static uint64_t uid(uint32_t *x, uint64_t a, uint64_t b) {
     const uint64_t past = uerange * scaling;
     do {
       ret = (uint64_t)mr_next(x) - 1u;
+      if (cen && ret >= urngrange - 31) cen[ret >= past]++;
     } while (ret >= past);
     ret /= scaling;
   } else {
@@ -149,6 +153,12 @@ typedef struct {
   uint8_t n_in_market;
   uint8_t in_market[COG_N_SHOP];
   uint32_t flags;
+  /* census: [phase: 0 inside orc_reset / orc_reset_default, 1 inside a step, 2 inside the auto-reset
+     that ends a step][ORC_SITE_*: deck draw, player_cards_from_active, map generation][accepted,
+     rejected]; per env, so that the threaded drivers (one env, one thread) count without sharing
+     anything */
+  uint32_t cen[3][3][2];
+  uint8_t phase;
   omap m;
   /* views into the vec buffers */
   cog_obs_t *obs;
@@ -333,7 +343,7 @@ static int overlap(pt *p1, int n1, const pt *p2src, int n2, pt *scratch) {  /* m
   return found;
 }
 
-static int add_random_piece(omap *m, int id, uint32_t *rng) {   /* map.cpp:277-307 */
+static int add_random_piece(omap *m, int id, uint32_t *rng, uint32_t *cen) {   /* map.cpp:277-307 */
   piece_t *p = &m->pc[id];
   piece_reset(p);
   int ncand = 0;
@@ -368,9 +378,9 @@ static int add_random_piece(omap *m, int id, uint32_t *rng) {   /* map.cpp:277-3
   free(scratch);
   int ok = 0;
   if (nvalid) {
-    uint64_t idx = uid(rng, 0, (uint64_t)nvalid - 1);
+    uint64_t idx = uid(rng, 0, (uint64_t)nvalid - 1, cen);
     conn_t c = valid[idx];
-    uint64_t ri = uid(rng, 0, (uint64_t)c.nopt - 1);
+    uint64_t ri = uid(rng, 0, (uint64_t)c.nopt - 1, cen);
     add_piece(m, id, c.c, c.opt[ri]);
     ok = 1;
   }
@@ -406,7 +416,8 @@ static int generate(oenv *e, int failures, uint32_t rng) {  /* map.cpp:697-742; 
   if (failures >= COG_MAX_FAILURES) { e->flags |= ORC_F_MAPGEN_FAIL; return -1; }
   omap *m = &e->m;
   if (failures > m->gs_depth) m->gs_depth = failures;
-  uint64_t s = uid(&rng, 0, 1);
+  uint32_t *cen = e->cen[e->phase][ORC_SITE_MAP];
+  uint64_t s = uid(&rng, 0, 1, cen);
   pt origin = {0, 0};
   add_piece(m, COG_PIECE_START0 + (int)s, origin, 0);
   uint64_t valid[COG_N_TRAVEL];
@@ -417,16 +428,16 @@ static int generate(oenv *e, int failures, uint32_t rng) {  /* map.cpp:697-742; 
     int success;
     uint64_t next = 0;
     if (nvalid) {
-      next = valid[uid(&rng, 0, (uint64_t)nvalid - 1)];
-      success = add_random_piece(m, COG_PIECE_TRAVEL0 + (int)next, &rng);
+      next = valid[uid(&rng, 0, (uint64_t)nvalid - 1, cen)];
+      success = add_random_piece(m, COG_PIECE_TRAVEL0 + (int)next, &rng, cen);
     } else {
       success = 0;
     }
     if (success) erase_gcc13(valid, &nvalid, next, &e->flags);
     else if (generate(e, failures + 1, rng)) return -1;
   }
-  uint64_t en = uid(&rng, 0, 1);
-  if (!add_random_piece(m, COG_PIECE_END0 + (int)en, &rng)) {
+  uint64_t en = uid(&rng, 0, 1, cen);
+  if (!add_random_piece(m, COG_PIECE_END0 + (int)en, &rng, cen)) {
     map_reset(m);
     if (generate(e, failures + 1, rng)) return -1;
   }
@@ -488,7 +499,7 @@ static void deck_draw(oenv *e, int p, uint8_t n) {         /* cards.cpp:183-211 
   if (P->n_in_draw < n) deck_move_discard_to_draw(e, p);
   if (n > P->n_in_draw) n = P->n_in_draw;
   for (int i = 0; i < n; i++) {
-    uint64_t t = uid(&e->rng, 0, (uint64_t)P->n_in_draw - 1);
+    uint64_t t = uid(&e->rng, 0, (uint64_t)P->n_in_draw - 1, e->cen[e->phase][ORC_SITE_DECK]);
     size_t c = scan(e, d, COG_DECK_DRAW, t);
     d[COG_DECK_DRAW + c]--;
     P->n_in_draw--;
@@ -562,7 +573,7 @@ static void player_cards_from_active(oenv *e, int p, uint8_t n, int discard) {
     n = avail;
   }
   for (uint8_t i = 0; i < n; i++) {
-    uint64_t t = uid(&e->rng, 0, (uint64_t)(avail - 1 - i));
+    uint64_t t = uid(&e->rng, 0, (uint64_t)(avail - 1 - i), e->cen[e->phase][ORC_SITE_ACTIVE]);
     size_t c = scan(e, d, COG_DECK_ACTIVE, t);
     P->n_active--;
     d[COG_DECK_ACTIVE + c]--;
@@ -881,6 +892,7 @@ int orc_reset(orc_vec *v, uint32_t seed, uint8_t n_players, uint8_t n_pieces, in
     e->max_steps = max_steps;
     e->seed = (uint32_t)(seed + (uint32_t)i);
     e->rng = mr_seed(e->seed);
+    e->phase = 0;
     if (env_reset(e)) return -1;
   }
   return 0;
@@ -898,6 +910,7 @@ static void *reset_worker(void *p) {
       e->seed = (uint32_t)(a->seed + (uint32_t)i);
       e->rng = mr_seed(e->seed);
     }
+    e->phase = 0;
     if (env_reset(e)) a->rc = -1;
   }
   return NULL;
@@ -930,8 +943,10 @@ static int reset_threads(orc_vec *v, uint32_t seed, uint8_t n_players, uint8_t n
 }
 
 int orc_reset_default(orc_vec *v) {
-  for (size_t i = 0; i < v->n; i++)
+  for (size_t i = 0; i < v->n; i++) {
+    v->env[i].phase = 0;
     if (env_reset(&v->env[i])) return -1;
+  }
   return 0;
 }
 
@@ -940,8 +955,10 @@ int orc_step_range(orc_vec *v, const void *actions, size_t lo, size_t hi) {
   int rc = 0;
   for (size_t i = lo; i < hi; i++) {           /* vec_cog_env::step_single, :53-61 */
     oenv *e = &v->env[i];
+    e->phase = 1;
     env_step(e, &a[i]);
     v->dones[i] = e->done;
+    e->phase = 2;
     if (e->done && v->autoreset && env_reset(e)) rc = -1;
     v->agent_sel[i] = e->agent;
   }
@@ -961,6 +978,9 @@ uint8_t *orc_agent_sel(orc_vec *v) { return v->agent_sel; }
 void *orc_infos(orc_vec *v) { return v->infos; }
 uint32_t orc_flags(const orc_vec *v, size_t i) { return v->env[i].flags; }
 void orc_clear_flags(orc_vec *v) { for (size_t i = 0; i < v->n; i++) v->env[i].flags = 0; }
+
+void orc_census_clear(orc_vec *v) { for (size_t i = 0; i < v->n; i++) memset(v->env[i].cen, 0, sizeof(v->env[i].cen)); }
+void orc_census(const orc_vec *v, size_t i, uint32_t *out) { memcpy(out, v->env[i].cen, sizeof(v->env[i].cen)); }
 
 int orc_debug_state(const orc_vec *v, size_t i, uint32_t *out, size_t n_out) {
   const oenv *e = &v->env[i];
@@ -1019,6 +1039,7 @@ struct orc_sampler {
   size_t n;
   uint32_t *rng;
   cog_action_t *actions;
+  uint32_t (*cen)[2][2];   /* census per sampler: [a head with one candidate, with two or more][accepted, rejected] */
 };
 
 /* sampler i seeded seed + first + i in size_t (vec_sampler.h:9-13: seed + i, seed a u32; first: the
@@ -1027,6 +1048,7 @@ orc_sampler *orc_sampler_create_at(size_t n, uint32_t seed, uint64_t first) {
   orc_sampler *s = (orc_sampler *)calloc(1, sizeof(orc_sampler));
   s->n = n;
   s->rng = (uint32_t *)calloc(n + 1, sizeof(uint32_t));
+  s->cen = (uint32_t (*)[2][2])calloc(n + 1, sizeof(*s->cen));
   s->actions = (cog_action_t *)aligned_alloc(64, n * sizeof(cog_action_t) + 64);
   memset(s->actions, 0, n * sizeof(cog_action_t));
   for (size_t i = 0; i < n; i++) s->rng[i] = mr_seed((uint64_t)seed + first + (uint64_t)i);
@@ -1035,16 +1057,20 @@ orc_sampler *orc_sampler_create_at(size_t n, uint32_t seed, uint64_t first) {
 orc_sampler *orc_sampler_create(size_t n, uint32_t seed) { return orc_sampler_create_at(n, seed, 0); }
 void orc_sampler_destroy(orc_sampler *s) {
   if (!s) return;
-  free(s->rng); free(s->actions); free(s);
+  free(s->rng); free(s->cen); free(s->actions); free(s);
 }
 
-static uint8_t sample_head(uint32_t *rng, const uint8_t *m, int len) {
+uint32_t orc_sampler_state(const orc_sampler *s, size_t i) { return s->rng[i]; }
+void orc_sampler_census_clear(orc_sampler *s) { memset(s->cen, 0, s->n * sizeof(*s->cen)); }
+void orc_sampler_census(const orc_sampler *s, size_t i, uint32_t *out) { memcpy(out, s->cen[i], sizeof(*s->cen)); }
+
+static uint8_t sample_head(uint32_t *rng, uint32_t (*cen)[2], const uint8_t *m, int len) {
   uint8_t valid[32];
   int k = 0;
   for (int i = 0; i < len; i++)
     if (m[i]) valid[k++] = (uint8_t)i;
   if (!k) return 0;
-  return valid[uid(rng, 0, (uint64_t)k - 1)];
+  return valid[uid(rng, 0, (uint64_t)k - 1, cen[k > 1])];
 }
 
 void orc_sample_range(orc_sampler *s, const void *masks, size_t lo, size_t hi) {
@@ -1052,11 +1078,12 @@ void orc_sample_range(orc_sampler *s, const void *masks, size_t lo, size_t hi) {
   for (size_t i = lo; i < hi; i++) {
     cog_action_t *a = &s->actions[i];
     uint32_t *r = &s->rng[i];
-    a->play = sample_head(r, m[i].play, 22);
-    a->play_special = sample_head(r, m[i].play_special, 22);
-    a->remove = sample_head(r, m[i].remove, 22);
-    a->move = sample_head(r, m[i].move, 7);
-    a->get_from_shop = sample_head(r, m[i].get_from_shop, 19);
+    uint32_t (*c)[2] = s->cen[i];
+    a->play = sample_head(r, c, m[i].play, 22);
+    a->play_special = sample_head(r, c, m[i].play_special, 22);
+    a->remove = sample_head(r, c, m[i].remove, 22);
+    a->move = sample_head(r, c, m[i].move, 7);
+    a->get_from_shop = sample_head(r, c, m[i].get_from_shop, 19);
   }
 }
 void orc_sample(orc_sampler *s, const void *masks) { orc_sample_range(s, masks, 0, s->n); }
@@ -1068,11 +1095,12 @@ void orc_sample_stored_range(orc_sampler *s, const orc_vec *v, size_t lo, size_t
     const cog_action_mask_t *m = &v->obs[i].player_data[v->env[i].agent].action_mask;
     cog_action_t *a = &s->actions[i];
     uint32_t *r = &s->rng[i];
-    a->play = sample_head(r, m->play, 22);
-    a->play_special = sample_head(r, m->play_special, 22);
-    a->remove = sample_head(r, m->remove, 22);
-    a->move = sample_head(r, m->move, 7);
-    a->get_from_shop = sample_head(r, m->get_from_shop, 19);
+    uint32_t (*c)[2] = s->cen[i];
+    a->play = sample_head(r, c, m->play, 22);
+    a->play_special = sample_head(r, c, m->play_special, 22);
+    a->remove = sample_head(r, c, m->remove, 22);
+    a->move = sample_head(r, c, m->move, 7);
+    a->get_from_shop = sample_head(r, c, m->get_from_shop, 19);
   }
 }
 void *orc_sampler_actions(orc_sampler *s) { return s->actions; }
@@ -1099,6 +1127,17 @@ static void *worker(void *p) {
     pthread_barrier_wait(w->bar);                           /* step_sync per step */
   }
   return NULL;
+}
+
+/* the same loop on the calling thread (the searches of tests/planted_cases.py: thousands of 1-env runs) */
+int orc_run(orc_vec *v, orc_sampler *s, int steps, int stored) {
+  int rc = 0;
+  for (int t = 0; t < steps; t++) {
+    if (stored) orc_sample_stored_range(s, v, 0, v->n);
+    else orc_sample_range(s, v->sel, 0, v->n);
+    rc |= orc_step_range(v, s->actions, 0, v->n);
+  }
+  return rc;
 }
 
 double orc_run_threaded(orc_vec *v, orc_sampler *s, int steps, int n_threads) {

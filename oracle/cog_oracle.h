@@ -72,6 +72,20 @@ int orc_debug_state(const orc_vec *v, size_t i, uint32_t *out, size_t n_out);
 #define ORC_GEN_STATS 12
 int orc_gen_stats(const orc_vec *v, size_t i, int32_t *out, size_t n_out);
 
+/* Census of the draws that can be rejected: every draw r of uniform_int_distribution with
+ * r >= 2147483645 - 31 (the top 32 values of minstd_rand0's range; a draw below them is accepted by
+ * every range of this game) is counted as accepted or rejected (r >= k * (2147483645 / k) for a pile
+ * of k; r == 2147483645 is rejected by every k), by site and by phase.  Counters are per env and per
+ * sampler (nothing shared between the threads of orc_run_threaded) and decide nothing.
+ * orc_census: out[18] = [phase][site][class], phase 0 inside orc_reset* / orc_reset_default*, 1 inside
+ * a step, 2 inside the auto-reset that ends a step (its map generation and initial hands); class 0
+ * accepted, 1 rejected. */
+#define ORC_SITE_DECK 0     /* deck_draw: initial hands, turn ends, the draw specials */
+#define ORC_SITE_ACTIVE 1   /* player_cards_from_active: discards and removes paid for a move */
+#define ORC_SITE_MAP 2      /* generate / add_random_piece */
+void orc_census_clear(orc_vec *v);
+void orc_census(const orc_vec *v, size_t i, uint32_t *out);
+
 orc_sampler *orc_sampler_create(size_t n, uint32_t seed);
 orc_sampler *orc_sampler_create_at(size_t n, uint32_t seed, uint64_t first);   /* seeds seed + first + i */
 void orc_sampler_destroy(orc_sampler *s);
@@ -81,11 +95,17 @@ void orc_sample_range(orc_sampler *s, const void *masks, size_t lo, size_t hi);
  * agent_selections view, which a reset leaves stale): the full-dynamics driver */
 void orc_sample_stored_range(orc_sampler *s, const orc_vec *v, size_t lo, size_t hi);
 void *orc_sampler_actions(orc_sampler *s);            /* ActionData[n] */
+uint32_t orc_sampler_state(const orc_sampler *s, size_t i);   /* sampler i's generator state */
+/* out[4] = [a head with one candidate, a head with two or more][accepted, rejected] (see orc_census) */
+void orc_sampler_census_clear(orc_sampler *s);
+void orc_sampler_census(const orc_sampler *s, size_t i, uint32_t *out);
 
 /* reference ThreadedRunner shape (runner.h:21-64): contiguous env blocks, one pinned worker
  * per block, per step "sample(selected masks); step(actions)" then a barrier.
  * Returns wall seconds for `steps` steps. */
 double orc_run_threaded(orc_vec *v, orc_sampler *s, int steps, int n_threads);
+/* `steps` x (sample; step) on the calling thread; 0, or -1 after a failed map generation */
+int orc_run(orc_vec *v, orc_sampler *s, int steps, int stored);
 /* the same loop; stored != 0 samples each env's current agent's stored mask instead */
 double orc_run_threaded_masks(orc_vec *v, orc_sampler *s, int steps, int n_threads, int stored);
 

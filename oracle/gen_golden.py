@@ -19,6 +19,7 @@ env i of a batch == a 1-env batch seeded seed+i, sampler seeded sseed+i).
     python oracle/gen_golden.py --lategame   # ref_lategame.json + ref_lategame_digests.npz only
     python oracle/gen_golden.py --bigmaps    # ref_maps_big.json only
     python oracle/gen_golden.py --corners    # ref_corners.json + ref_corners_digests.npz only
+    python oracle/gen_golden.py --planted    # ref_planted.json + ref_planted_digests.npz only
 """
 from __future__ import annotations
 
@@ -402,6 +403,70 @@ def corners():
                        sets=sets), f)
 
 
+def planted_safe_steps(pc, case):
+    """Steps of `case` the reference can run, from the oracle's flags after the reset(s) and after every
+    step (-1: not even the resets; a failed map generation ends the run like a flag)."""
+    o, s = po.OracleVec(1), po.OracleSampler(1, case.sampler_seed + pc.IDX)
+    try:
+        o.reset(case.env_seed + pc.IDX, case.players, 3, 2, case.max_steps)
+        if case.group == "reset0":
+            o.reset_default()
+    except RuntimeError:
+        return -1
+    if o.flags(0) & po.REF_UNSAFE:
+        return -1
+    agent = 0
+    for t in range(case.steps):
+        s.sample(o.observations["player_data"]["action_mask"][:, agent].copy() if case.mode == "sto" else o.selected_action_masks)
+        try:
+            o.step(s.actions)
+        except RuntimeError:
+            return t
+        if o.flags(0) & po.REF_UNSAFE:
+            return t
+        agent = 0 if o.dones[0] else int(o.agent_selection[0])
+    return case.steps
+
+
+def planted():
+    """The planted draws (tests/planted_cases.py), pinned by the reference: for the planted env alone,
+    the reference's digests after the reset(s) and after every step it can run of every case."""
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+    import planted_cases as pc
+    keys, lengths, digs = [], [], []
+    out_reset, cut, whole = 0, 0, 0
+    for case in pc.all_cases():
+        L = planted_safe_steps(pc, case)
+        if L < 0:
+            out_reset += 1
+            continue
+        cut += int(L < case.steps)
+        whole += int(L == case.steps)
+        run = case._replace(steps=L)
+        d = pc.trace_digests(po.RefVec1(), po.RefSampler1(case.sampler_seed + pc.IDX), run)
+        if not np.array_equal(d, pc.trace_digests(po.OracleVec(1), po.OracleSampler(1, case.sampler_seed + pc.IDX), run)):
+            raise SystemExit(f"oracle != reference: planted case {case}")
+        keys.append(pc.case_key(case))
+        lengths.append(L)
+        digs.append(d)
+    np.savez(os.path.join(OUT, "ref_planted_digests.npz"), digests=np.concatenate(digs))
+    with open(os.path.join(OUT, "ref_planted.json"), "w") as f:
+        json.dump(dict(source="oracle/_ref (unmodified reference core) via oracle/gen_golden.py --planted",
+                       digest="sha256[:8] over named leaves of obs, sel, rewards, dones, agent_sel, infos, actions, of the "
+                              "planted env alone (a 1-env batch seeded env seed + 37, sampler seed + 37)",
+                       digests_file="ref_planted_digests.npz (digests: the cases one after another, each uint8[steps[k] + 1, "
+                                    "8]: after the reset(s), then after every step)",
+                       key="group:env seed:sampler seed:players:max_steps:mask mode:steps of the case",
+                       screened=dict(cases=len(keys) + out_reset, recorded_whole=whole, recorded_cut=cut, left_out=out_reset,
+                                     why="the reference built against libstdc++ 11 cannot run past a REF_UNSAFE flag of "
+                                         "the oracle (an erase past the end of valid_indices, a B start with fewer than 4 "
+                                         "players, a lookup outside hex_array) or a failed map generation: a case whose "
+                                         "reset raises one is left out, a case whose step t raises one is recorded up to "
+                                         "step t - 1"),
+                       keys=keys, steps=lengths), f, separators=(",", ":"))
+    print(f"planted: {len(keys)} cases recorded ({whole} whole, {cut} cut at a hazard), {out_reset} left out")
+
+
 def main():
     assert po.ref_available(), "build the reference first: make -C oracle ref"
     os.makedirs(OUT, exist_ok=True)
@@ -416,6 +481,9 @@ def main():
         return
     if "--corners" in sys.argv:
         corners()
+        return
+    if "--planted" in sys.argv:
+        planted()
         return
     t = traces()
     arrays = {}

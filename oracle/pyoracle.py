@@ -45,6 +45,8 @@ F_GRID_OVER, F_OOB_LOOKUP, F_SCAN_OVER, F_B_START_LT4 = 0x10, 0x20, 0x40, 0x80
 # seeds with any of these cannot be run by the reference built against libstdc++ 11
 REF_UNSAFE = F_ERASE_PAST | F_Q9_OOB | F_GRID_OVER | F_OOB_LOOKUP | F_SCAN_OVER | F_B_START_LT4 | F_Q24_CLAMP
 # orc_gen_stats, in its order (cog_oracle.h)
+# orc_census / orc_sampler_census, in their order (cog_oracle.h)
+CENSUS_PHASES, CENSUS_SITES, CENSUS_HEADS = ("reset", "step", "autoreset"), ("deck", "active", "map"), ("one", "many")
 GEN_STATS = ("total", "placed", "depth", "cmin", "cmax", "dimx", "dimy", "sx0", "sx1", "sy0", "sy1", "offlat")
 
 
@@ -145,6 +147,13 @@ class _Lib:
             lib.orc_run_threaded_masks.restype = C.c_double
             lib.orc_run_threaded_masks.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
             lib.orc_sample_stored_range.argtypes = [vp, vp, sz, sz]
+            lib.orc_run.argtypes = [vp, vp, C.c_int, C.c_int]
+            lib.orc_census_clear.argtypes = [vp]
+            lib.orc_census.argtypes = [vp, sz, C.POINTER(C.c_uint32)]
+            lib.orc_sampler_state.restype = C.c_uint32
+            lib.orc_sampler_state.argtypes = [vp, sz]
+            lib.orc_sampler_census_clear.argtypes = [vp]
+            lib.orc_sampler_census.argtypes = [vp, sz, C.POINTER(C.c_uint32)]
             cls._oracle = lib
         return cls._oracle
 
@@ -233,6 +242,16 @@ class OracleVec:
     def clear_flags(self):
         self.lib.orc_clear_flags(self.h)
 
+    def census(self, i):
+        """uint32[3, 3, 2] of env i: [CENSUS_PHASES][CENSUS_SITES][accepted, rejected] counts of its
+        draws within 31 of the top of the generator's range (cog_oracle.h orc_census)."""
+        out = (C.c_uint32 * 18)()
+        self.lib.orc_census(self.h, i, out)
+        return np.array(out[:], dtype=np.uint32).reshape(3, 3, 2)
+
+    def census_clear(self):
+        self.lib.orc_census_clear(self.h)
+
     def debug_state(self, i):
         out = (C.c_uint32 * 64)()
         k = self.lib.orc_debug_state(self.h, i, out, 64)
@@ -296,6 +315,19 @@ class OracleSampler:
         masks = np.ascontiguousarray(masks, dtype=MASK)
         self.lib.orc_sample(self.h, masks.ctypes.data)
 
+    def state(self, i):
+        """Sampler i's generator state."""
+        return int(self.lib.orc_sampler_state(self.h, i))
+
+    def census(self, i):
+        """uint32[2, 2] of sampler i: [a head with one candidate, with two or more][accepted, rejected]."""
+        out = (C.c_uint32 * 4)()
+        self.lib.orc_sampler_census(self.h, i, out)
+        return np.array(out[:], dtype=np.uint32).reshape(2, 2)
+
+    def census_clear(self):
+        self.lib.orc_sampler_census_clear(self.h)
+
     def sample_stored(self, vec):
         """sample() from the stored mask of every env's own current agent, as the stored-mask
         kernels do (after a reset that is agent 0, whatever the agent_selection view still shows)."""
@@ -335,6 +367,11 @@ def run_threaded(vec: OracleVec, sampler: OracleSampler, steps: int, n_threads: 
     return _Lib.oracle().orc_run_threaded(vec.h, sampler.h, steps, n_threads)
 
 
+def run(vec: OracleVec, sampler: OracleSampler, steps: int, stored: bool = False) -> bool:
+    """`steps` x (sample; step) inside the oracle on this thread; False after a failed map generation."""
+    return _Lib.oracle().orc_run(vec.h, sampler.h, steps, 1 if stored else 0) == 0
+
+
 class RefVec1:
     """The reference's own vec_cog_env<1> (dev container only; screened seeds only)."""
 
@@ -352,6 +389,10 @@ class RefVec1:
 
     def reset(self, seed, n_players=4, n_pieces=3, difficulty=0, max_steps=100000):
         if self.lib.ref_reset(self.h, seed & 0xFFFFFFFF, n_players, n_pieces, int(difficulty), max_steps):
+            raise RuntimeError("Failed to generate map in specified maximum number of attempts")
+
+    def reset_default(self):
+        if self.lib.ref_reset_default(self.h):
             raise RuntimeError("Failed to generate map in specified maximum number of attempts")
 
     def step(self, actions):

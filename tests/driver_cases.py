@@ -111,11 +111,12 @@ def wide_envs(orc):
 class Harness:
     """One engine handle (env, sampler, its runners) and the oracle pair that mirrors it.  cg=None:
     the oracle side alone (the CPU census).  threads > 0: the oracle's rollouts and resets run on
-    that many host threads (the large batches)."""
+    that many host threads (the large batches).  first: the sampler's first_index (sampler i is seeded
+    sampler_seed + first + i)."""
 
-    def __init__(self, cg, n, sampler_seed, device=None, threads=0, lazy_views=False):
-        self.cg, self.n, self.threads = cg, n, threads
-        self.orc, self.osm = po.OracleVec(n), po.OracleSampler(n, sampler_seed)
+    def __init__(self, cg, n, sampler_seed, device=None, threads=0, lazy_views=False, first=0):
+        self.cg, self.n, self.threads, self.first = cg, n, threads, first
+        self.orc, self.osm = po.OracleVec(n), po.OracleSampler(n, sampler_seed, first)
         self.last = np.zeros(n, dtype=po.ACTION)             # what the sampler's device actions hold
         self.logits = logits_table(n)
         self.autoreset, self.players, self.max_steps = True, 4, 100000
@@ -126,10 +127,20 @@ class Harness:
         self.ends, self.op_ends, self.wide_max = 0, [], 0
         self.cdeck, self.trio_loaded, self.trio_clear = False, 0, 0
         if cg is not None:
-            kw = {} if device is None else {"device": device}
+            kw = self.kw = {} if device is None else {"device": device}
             self.env = cg.vec.get_vec_env(n)(**kw)
-            self.smp = cg.vec.get_vec_sampler(n)(sampler_seed, **kw)
+            self.smp = cg.vec.get_vec_sampler(n)(sampler_seed, first_index=first, **kw)
             self.runners, self.t_logits = {}, None
+
+    def new_sampler(self, sampler_seed):
+        """The sampler made anew for `sampler_seed` on both sides (tests/planted_cases.py: a seed is a
+        generator state); the runners, which hold the old sampler, go with it."""
+        self.osm = po.OracleSampler(self.n, sampler_seed, self.first)
+        self.last = np.zeros(self.n, dtype=po.ACTION)
+        self.acts_fresh = False
+        if self.cg is not None:
+            self.runners = {}
+            self.smp = self.cg.vec.get_vec_sampler(self.n)(sampler_seed, first_index=self.first, **self.kw)
 
     # ---- engine parts --------------------------------------------------------------------------
     def runner(self, stored, device_views):
@@ -159,6 +170,15 @@ class Harness:
         if self.acts_fresh:
             bad = po.named_equal(self.smp.get_actions(), self.last)
             assert bad is None, f"{what}: the sampler's actions view differs in {bad}"
+
+    def compare_device_actions(self, what):
+        """The sampler's device actions against the oracle sampler's (a single shard, through torch)."""
+        import torch
+        acts = torch.from_dlpack(self.smp.dlpack()).cpu().numpy().view(po.ACTION).reshape(self.n)
+        bad = po.named_equal(acts, self.last)
+        if bad is not None:
+            i = int(np.nonzero(acts[bad] != self.last[bad])[0][0])
+            raise AssertionError(f"{what}: the sampler's device actions differ in {bad} (first at env {i})")
 
     def compare_hazards(self, what):
         per = self.env.hazards()[1]

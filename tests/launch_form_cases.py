@@ -62,9 +62,16 @@ CORNERS_HOST_SEQS = {"one player": [X(77, 1, 8)] + HOST_SEQ[1:],
                      "max_steps 0": [X(77, 4, 0)] + [(d, min(k, CORNERS_HOST_MS0_STEPS)) for d, k in HOST_SEQ[1:]]}
 
 
+# the planted draws (tests/planted_cases.py): the reduced list -- a case per census cell, a sampler
+# rejection at every launch position, the case with two events -- at 70 envs with the planted one at
+# index 37, under the rollout drivers or (COG_NO_SPEC) the host drivers
+PLANTED_DRIVERS, PLANTED_HOST_DRIVERS = ("T20", "S20"), ("H", "Hc", "Hs", "R1", "L", "Ls")
+PLANTED_N = 70
+
+
 class Row:
     """env: the switches; sizes: the batch sizes it runs at; seq: "rollout" | "rollout+2p" | "redo" |
-    "big" | "host" | "corners" | "corners-host"; kinds: what rollout_kind must say for (players, stored) -> name."""
+    "big" | "host" | "corners" | "corners-host" | "planted" | "planted-host"; kinds: what rollout_kind must say for (players, stored) -> name."""
 
     def __init__(self, name, env, seq="rollout", sizes=SIZES, kinds=None):
         self.name, self.env, self.seq, self.sizes = name, dict(env), seq, tuple(sizes)
@@ -108,6 +115,15 @@ ROWS = {r.name: r for r in (
     Row("corners-wave", {"COG_ROLLOUT": "wave"}, seq="corners", kinds=_all("wave")),
     Row("corners-host-no-zerocopy", {"COG_NO_ZEROCOPY": "1"}, seq="corners-host", sizes=(200,)),
     Row("corners-host-no-spec", {"COG_NO_SPEC": "1"}, seq="corners-host", sizes=(200,)),
+    # the draws that reject (the non-LAT trio's sample_lean takes uid_tab_accepted, not the index table)
+    Row("planted-no-lat", {"COG_TRIO_JT": "0"}, seq="planted", sizes=(PLANTED_N,)),
+    Row("planted-lat", {"COG_TRIO_JT": "1"}, seq="planted", sizes=(PLANTED_N,)),
+    Row("planted-epw32", {"COG_TRIO_EPW": "32"}, seq="planted", sizes=(PLANTED_N,)),
+    Row("planted-duo", {"COG_TRIO": "0"}, seq="planted", sizes=(PLANTED_N,),
+        kinds={(4, False): "duo", (3, False): "duo", (2, False): "duo", (4, True): "duo"}),
+    Row("planted-pipe", {"COG_ROLLOUT": "pipe"}, seq="planted", sizes=(PLANTED_N,), kinds=_all("pipe")),
+    Row("planted-wave", {"COG_ROLLOUT": "wave"}, seq="planted", sizes=(PLANTED_N,), kinds=_all("wave")),
+    Row("planted-host-no-spec", {"COG_NO_SPEC": "1"}, seq="planted-host", sizes=(PLANTED_N,)),
 )}
 CASES = [(r.name, n) for r in ROWS.values() for n in r.sizes]
 SWITCHES = sorted({k for r in ROWS.values() for k in r.env} | {"COG_SPIN_US", "COG_RUNNER_CHUNK", "COG_DEBUG_PARK_NOFIX"})
@@ -168,7 +184,8 @@ def check_form(row, n, form, kinds):
 
 
 def child_main(argv):
-    """argv: row name, n.  Run in a child process whose environment carries the row's switches."""
+    """argv: row name, n, for the planted rows the file of their cases (the parent's search, as JSON).
+    Run in a child process whose environment carries the row's switches."""
     import city_of_gold as cg
     import pyoracle as po
     row, n = ROWS[argv[0]], int(argv[1])
@@ -179,7 +196,19 @@ def child_main(argv):
     check_form(row, n, form, kinds)
     out = dict(row=row.name, n=n, form=form, kinds=kinds)
     seq = sequence_of(row)
-    if row.seq in ("host", "corners-host"):
+    if row.seq in ("planted", "planted-host"):
+        import planted_cases as pc
+        with open(argv[2]) as f:
+            cases = [pc.Case(*[tuple(x) if isinstance(x, list) else x for x in c]) for c in json.load(f)]
+        assert n == pc.N and len(cases) >= 16
+        h = dc.Harness(cg, n, pc.PLAIN_SAMPLER_SEED)
+        for driver in (PLANTED_DRIVERS if row.seq == "planted" else PLANTED_HOST_DRIVERS):
+            for case in cases:
+                pc.walk(h, case, driver, f"{row.name}, {driver}", device_actions=False)
+                if "COG_NO_SPEC" in row.env:
+                    assert h.smp.spec_stats()[1] == 0, f"{driver}: a speculative sample taken under COG_NO_SPEC"
+        out["ends"], out["cases"] = h.ends, len(cases)
+    elif row.seq in ("host", "corners-host"):
         spec_off = "COG_NO_SPEC" in row.env
         walks = (("one shard", {}, n, seq), ("two shards", {"device": [0, 0]}, HOST_TWO_SHARD_N, seq),
                  ("lazy views", {"lazy_views": True}, dc.PAIR_N, dc.LAZY_VIEWS_CASE))

@@ -33,6 +33,12 @@ checks again.
                    COG_TRIO=0 and COG_ROLLOUT=pipe / wave (one player selects like two: rollout_kind is
                    asserted for 1 player too); the host walk after a reset with one player and (70
                    envs, 8 steps per op) at max_steps 0 under COG_NO_ZEROCOPY and COG_NO_SPEC
+  planted-*        the draws that reject (tests/planted_cases.py: a case per census cell, a sampler rejection
+                   at every launch position, the case with two events; 70 envs, the planted one at index
+                   37) under T20 and S20 with COG_TRIO_JT=0 (sample_lean's uid_tab_accepted branch) and 1,
+                   COG_TRIO_EPW=32 (lane 5 of the second workgroup), COG_TRIO=0, COG_ROLLOUT=pipe / wave,
+                   and under H Hc Hs R1 L Ls with COG_NO_SPEC; the parent searches the cases once and
+                   hands them to the child as a file
   encode           env.time_encode(1, variant) for the production kernel (0), k_encode_lds<false> (1)
                    and k_encode_direct (2): observations equal their copy and the oracle; then the
                    map bytes of the device records are overwritten with 0xEE and the kernel must put
@@ -111,7 +117,7 @@ def stop_after_a_crash():
         pytest.skip("an earlier case of this module crashed: " + CRASHED[0])
 
 
-def run_child(cg, tmp_path, row, n, timeout):
+def run_child(cg, tmp_path, row, n, timeout, extra=()):
     tests = os.path.dirname(os.path.abspath(__file__))
     pkg = os.path.dirname(os.path.dirname(cg.__file__))
     oracle_dir = os.path.dirname(os.path.abspath(po.__file__))
@@ -121,7 +127,7 @@ def run_child(cg, tmp_path, row, n, timeout):
     env.update(row.env, COG_NO_TORCH="1")                  # (no sequence here has a G or D op)
     what = f"{row.name} at n = {n}"
     try:
-        r = subprocess.run([sys.executable, str(script), tests, pkg, oracle_dir, row.name, str(n)], capture_output=True,
+        r = subprocess.run([sys.executable, str(script), tests, pkg, oracle_dir, row.name, str(n), *extra], capture_output=True,
                            text=True, timeout=timeout, env=env)
     except subprocess.TimeoutExpired:
         CRASHED.append(f"{what} ran into its timeout of {timeout} s")
@@ -140,7 +146,14 @@ def run_child(cg, tmp_path, row, n, timeout):
 @pytest.mark.parametrize("name,n", lf.CASES, ids=[f"{r}-n{n}" for r, n in lf.CASES])
 def test_launch_form(cg, tmp_path, name, n):
     row = lf.ROWS[name]
-    out = run_child(cg, tmp_path, row, n, 240 if n > 4096 else 150)
+    extra = ()
+    if row.seq.startswith("planted"):
+        import planted_cases as pc
+        (tmp_path / "planted.json").write_text(json.dumps(pc.reduced_cases()))
+        extra = (str(tmp_path / "planted.json"),)
+    out = run_child(cg, tmp_path, row, n, 240 if n > 4096 else 150, extra)
+    if row.seq.startswith("planted"):
+        assert out["cases"] == len(pc.reduced_cases())
     assert out["form"]["cus"] == cg._city_of_gold.trio_form(n)["cus"]
     if row.seq == "host":
         if "COG_NO_SPEC" in row.env:
