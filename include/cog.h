@@ -145,7 +145,15 @@ COG_API int cog_env_reset(cog_env *env, uint32_t seed, uint8_t n_players, uint8_
 /* vec_cog_env::reset() (vec_environment.h:32-36): keep params, continue each env's rng. */
 COG_API int cog_env_reset_default(cog_env *env);
 /* vec_cog_env::step(actions) (vec_environment.h:46-61) with n == num_envs host ActionData
- * records; auto-resets finished envs; host views refreshed before return. */
+ * records; auto-resets finished envs; host views refreshed before return.
+ * An index past its head is clamped to the head's last entry and flagged COG_HAZ_BAD_ACTION.  An
+ * index inside its head that the mask does not allow is executed as the reference executes it
+ * (cog_env::step never reads the mask, environment.cpp:91-181: the first non-zero head of play,
+ * play_special, move, get_from_shop, remove, on u8 counters that wrap around -- a card played from an
+ * empty hand leaves 255 of it, a remove with none pending 255 pending removes, a purchase from an
+ * empty shop slot 255 cards in it -- and a move in a closed direction leaves the map; the hazard flags
+ * it can raise are COG_HAZ_Q24_CLAMP and COG_HAZ_OOB_LOOKUP).  It is not refused and not flagged
+ * COG_HAZ_BAD_ACTION.  The same holds for cog_env_step_device and the runner's step. */
 COG_API int cog_env_step(cog_env *env, const cog_action_t *actions, size_t n);
 /* same, actions already in device memory (e.g. a sampler's device actions); single-shard envs */
 COG_API int cog_env_step_device(cog_env *env, const void *d_actions, size_t n);

@@ -17,6 +17,9 @@
  *   oracle/_asan/harness_asan --corners    the scenarios of kCornerScen (tests/test_corners_cpu.py): max_steps 0
  *                                          (a reset with map generation for every env at every step) and 1,
  *                                          and one player (the turn passes back to the same player)
+ *   oracle/_asan/harness_asan --offmask    host actions inside their heads that no mask allows (tests/test_offmask_cpu.py):
+ *                                          every kind of tests/driver_cases.py's M op at max_steps 12 and 100000,
+ *                                          1 to 4 players, the altered bytes from this file's own generator
  *
  * Scenarios: the reference trace sets of tests/golden/ref_traces (oracle/gen_golden.py traces():
  * the stored-mask driver with auto-resets, B-start seeds, 2 and 3 players, the selected-mask
@@ -42,31 +45,75 @@ typedef struct {
   size_t n;
   int no_reset; /* steps run with orc_set_autoreset(v, 0); then reset_default, the switch on, `steps` again */
   int clamped;  /* 1: a tenth of the (env, head) slots hold the head's clamp value, legal or not */
+  int offmask;  /* 1 + the kind of kOffKinds: half the envs' actions altered inside their heads, no mask consulted */
 } scenario;
 
 static const scenario kScen[] = {
-    {"C2shape_sel_medium", 12345, 4, 3, 1, 100000, 12345, 0, 1000, 16, 0, 0},
-    {"C3shape_sel_hard", 12345, 4, 3, 2, 100000, 12345, 0, 1000, 16, 0, 0},
-    {"stored_hard_ms30", 7, 4, 3, 2, 30, 7, 1, 1500, 16, 0, 0},
-    {"stored_medium_ms40_bstart", 70000, 4, 3, 1, 40, 70000, 1, 1500, 16, 0, 0},
-    {"c1like_2p_medium_sel", 0, 2, 3, 1, 100000, 0, 0, 20000, 1, 0, 0},
-    {"c1like_2p_medium_sto", 0, 2, 3, 1, 100000, 0, 1, 5000, 1, 0, 0},
-    {"p3_hard_sto_ms60", 300, 3, 3, 2, 60, 300, 1, 1500, 8, 0, 0},
+    {"C2shape_sel_medium", 12345, 4, 3, 1, 100000, 12345, 0, 1000, 16, 0, 0, 0},
+    {"C3shape_sel_hard", 12345, 4, 3, 2, 100000, 12345, 0, 1000, 16, 0, 0, 0},
+    {"stored_hard_ms30", 7, 4, 3, 2, 30, 7, 1, 1500, 16, 0, 0, 0},
+    {"stored_medium_ms40_bstart", 70000, 4, 3, 1, 40, 70000, 1, 1500, 16, 0, 0, 0},
+    {"c1like_2p_medium_sel", 0, 2, 3, 1, 100000, 0, 0, 20000, 1, 0, 0, 0},
+    {"c1like_2p_medium_sto", 0, 2, 3, 1, 100000, 0, 1, 5000, 1, 0, 0, 0},
+    {"p3_hard_sto_ms60", 300, 3, 3, 2, 60, 300, 1, 1500, 8, 0, 0, 0},
 };
 static const scenario kDriverScen[] = {
-    {"stored_hard_ms8_noreset", 77, 4, 3, 2, 8, 77, 1, 120, 16, 1, 0},
-    {"sel_hard_ms8_noreset_3p", 77, 3, 3, 2, 8, 77, 0, 120, 16, 1, 0},
-    {"clamped_host_actions_sel", 77, 4, 3, 2, 8, 77, 0, 300, 16, 0, 1},
-    {"clamped_host_actions_sto", 78, 2, 3, 1, 12, 78, 1, 300, 16, 0, 1},
+    {"stored_hard_ms8_noreset", 77, 4, 3, 2, 8, 77, 1, 120, 16, 1, 0, 0},
+    {"sel_hard_ms8_noreset_3p", 77, 3, 3, 2, 8, 77, 0, 120, 16, 1, 0, 0},
+    {"clamped_host_actions_sel", 77, 4, 3, 2, 8, 77, 0, 300, 16, 0, 1, 0},
+    {"clamped_host_actions_sto", 78, 2, 3, 1, 12, 78, 1, 300, 16, 0, 1, 0},
 };
 
 static const scenario kCornerScen[] = {
-    {"sto_hard_ms0_4p", 77, 4, 3, 2, 0, 77, 1, 40, 16, 0, 0},
-    {"sto_hard_ms1_4p", 77, 4, 3, 2, 1, 77, 1, 120, 16, 0, 0},
-    {"sel_hard_ms1_3p", 77, 3, 3, 2, 1, 77, 0, 120, 16, 0, 0},
-    {"sto_hard_1p_ms8", 77, 1, 3, 2, 8, 77, 1, 300, 16, 0, 0},
-    {"sel_hard_1p_1piece", 177, 1, 1, 2, 100000, 177, 0, 1000, 16, 0, 0},
+    {"sto_hard_ms0_4p", 77, 4, 3, 2, 0, 77, 1, 40, 16, 0, 0, 0},
+    {"sto_hard_ms1_4p", 77, 4, 3, 2, 1, 77, 1, 120, 16, 0, 0, 0},
+    {"sel_hard_ms1_3p", 77, 3, 3, 2, 1, 77, 0, 120, 16, 0, 0, 0},
+    {"sto_hard_1p_ms8", 77, 1, 3, 2, 8, 77, 1, 300, 16, 0, 0, 0},
+    {"sel_hard_1p_1piece", 177, 1, 1, 2, 100000, 177, 0, 1000, 16, 0, 0, 0},
 };
+
+/* --offmask: kind k at max_steps 100000 and 12, the players rotating so that 1 to 4 meet both */
+static const char *kOffKinds[9] = {"single", "replace", "all", "play", "special", "remove", "move", "shop", "sweep"};
+#define N_OFF 18
+static scenario gOffScen[N_OFF];
+static char gOffName[N_OFF][48];
+
+static void off_scenarios(void) {
+  for (int q = 0; q < N_OFF; q++) {
+    const int kind = q / 2, ends = q & 1;
+    const int players = 1 + (kind + ends) % 4;
+    snprintf(gOffName[q], sizeof gOffName[q], "offmask_%s_%dp_ms%d", kOffKinds[kind], players, ends ? 12 : 100000);
+    const scenario sc = {gOffName[q], 909u + (uint32_t)q, (uint8_t)players, 3, 2, ends ? 12u : 100000u, 909u + (uint32_t)q,
+                         0, 300, 16, 0, 0, 1 + kind};
+    gOffScen[q] = sc;
+  }
+}
+
+static uint32_t lcg_next(uint32_t *x) {
+  *x = *x * 1664525u + 1013904223u;
+  return *x >> 8;
+}
+
+/* the M op's kinds (tests/driver_cases.py offmask_actions) on one ActionData record */
+static void off_alter(uint8_t *a, int kind, size_t i, int t, uint32_t *lcg) {
+  static const uint8_t top[5] = {21, 21, 21, 6, 18};
+  if (kind == 8) {                                         /* sweep: slot (i + t) mod 87 */
+    int slot = (int)((i + (size_t)t) % 87u), k = 0;
+    while (slot >= top[k]) slot -= top[k++];
+    for (int j = 0; j < 5; j++) a[j] = j == k ? (uint8_t)(slot + 1) : 0;
+    return;
+  }
+  const uint32_t hit = lcg_next(lcg) & 1u;
+  const int head = kind >= 3 ? kind - 3 : (int)(lcg_next(lcg) % 5u);
+  uint8_t v[5];
+  for (int j = 0; j < 5; j++) v[j] = (uint8_t)(lcg_next(lcg) % (uint32_t)(top[j] + (kind == 2 ? 1 : 0)) + (kind == 2 ? 0u : 1u));
+  if (!hit) return;
+  for (int j = 0; j < 5; j++) {
+    if (kind == 2) a[j] = v[j];                            /* all: every head uniform in 0..top */
+    else if (j == head) a[j] = v[j];                       /* one head uniform in 1..top */
+    else if (kind != 1) a[j] = 0;                          /* (replace keeps the other heads) */
+  }
+}
 
 static uint64_t fnv(uint64_t h, const void *p, size_t b) {
   const uint8_t *c = (const uint8_t *)p;
@@ -85,9 +132,12 @@ int main(int argc, char **argv) {
   int bad = 0;
   const int drivers = argc > 1 && !strcmp(argv[1], "--drivers");
   const int corners = argc > 1 && !strcmp(argv[1], "--corners");
-  const scenario *list = drivers ? kDriverScen : corners ? kCornerScen : kScen;
+  const int offmask = argc > 1 && !strcmp(argv[1], "--offmask");
+  if (offmask) off_scenarios();
+  const scenario *list = drivers ? kDriverScen : corners ? kCornerScen : offmask ? gOffScen : kScen;
   const size_t n_list = drivers   ? sizeof(kDriverScen) / sizeof(kDriverScen[0])
                         : corners ? sizeof(kCornerScen) / sizeof(kCornerScen[0])
+                        : offmask ? (size_t)N_OFF
                                   : sizeof(kScen) / sizeof(kScen[0]);
   for (size_t q = 0; q < n_list; q++) {
     const scenario *sc = &list[q];
@@ -129,6 +179,10 @@ int main(int argc, char **argv) {
             lcg = lcg * 1664525u + 1013904223u;
             if ((lcg >> 16) % 10u == 0u) a[i * COG_ACTION_BYTES + (size_t)k] = top[k];
           }
+      }
+      if (sc->offmask) {
+        uint8_t *a = (uint8_t *)orc_sampler_actions(s);
+        for (size_t i = 0; i < sc->n; i++) off_alter(a + i * COG_ACTION_BYTES, sc->offmask - 1, i, t, &lcg);
       }
       orc_step(v, orc_sampler_actions(s));
       h = fnv(h, orc_obs(v), sc->n * COG_OBS_BYTES);

@@ -20,6 +20,7 @@ env i of a batch == a 1-env batch seeded seed+i, sampler seeded sseed+i).
     python oracle/gen_golden.py --bigmaps    # ref_maps_big.json only
     python oracle/gen_golden.py --corners    # ref_corners.json + ref_corners_digests.npz only
     python oracle/gen_golden.py --planted    # ref_planted.json + ref_planted_digests.npz only
+    python oracle/gen_golden.py --offmask    # ref_offmask.json + ref_offmask_digests.npz only
 """
 from __future__ import annotations
 
@@ -467,9 +468,57 @@ def planted():
     print(f"planted: {len(keys)} cases recorded ({whole} whole, {cut} cut at a hazard), {out_reset} left out")
 
 
+def offmask():
+    """Host actions the mask forbids (tests/offmask_cases.py), pinned by the reference: single-env streams
+    of kinds single, replace and all with 4, 3 and 2 players, 300 steps with 60 % of the sampled actions
+    altered, each cut at the step before the oracle's first REF_UNSAFE flag.  Per group the first
+    STREAM_KEEP seeds that run STREAM_LEAST steps or more; the fixture holds the groups' parameters, each
+    stream's index, length and off-mask count, and the reference's digests.  The actions come from the
+    stream's seed (tests/offmask_cases.py Stream)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(HERE), "tests"))
+    import offmask_cases as oc
+    groups, digs = [], []
+    for kind in oc.STREAM_KINDS:
+        for players in oc.STREAM_PLAYERS:
+            index, steps, off = [], [], []
+            for i in range(oc.STREAM_SCREENED):
+                if len(index) == oc.STREAM_KEEP:
+                    break
+                L, k = oc.stream_safe_steps((kind, players, i))
+                if L < oc.STREAM_LEAST:
+                    continue
+                d = oc.stream_run(po.RefVec1(), po.RefSampler1(oc.stream_seed(kind, players) + i), oc.Stream(kind, players, i), L)
+                o = oc.stream_run(po.OracleVec(1), po.OracleSampler(1, oc.stream_seed(kind, players) + i),
+                                  oc.Stream(kind, players, i), L)
+                if not np.array_equal(d, o):
+                    t = int(np.nonzero((d != o).any(1))[0][0])
+                    raise SystemExit(f"oracle != reference: offmask stream {kind}, {players} players, index {i}, step {t}")
+                index.append(i)
+                steps.append(L)
+                off.append(k)
+                digs.append(d)
+            assert len(index) == oc.STREAM_KEEP, f"{kind}, {players} players: {len(index)} streams of {oc.STREAM_SCREENED} seeds"
+            print(f"offmask: {kind}, {players} players: indices {index}, steps {steps}, off-mask actions {off}")
+            groups.append(dict(kind=kind, n_players=players, seed=oc.stream_seed(kind, players), index=index, steps=steps,
+                               off_mask=off))
+    np.savez(os.path.join(OUT, "ref_offmask_digests.npz"), digests=np.concatenate(digs))
+    with open(os.path.join(OUT, "ref_offmask.json"), "w") as f:
+        json.dump(dict(source="oracle/_ref (unmodified reference core) via oracle/gen_golden.py --offmask",
+                       digest="sha256[:8] over named leaves of obs, sel, rewards, dones, agent_sel, infos, actions",
+                       digests_file="ref_offmask_digests.npz (digests: the streams one after another in group order, each "
+                                    "uint8[steps[k] + 1, 8]: after the reset, then after every step)",
+                       stream="env seed + index[k] and sampler seed + index[k], n_pieces 3, HARD, max_steps 100000, the "
+                              "sampler on the selected mask, then the action altered as tests/offmask_cases.py Stream does "
+                              f"(fraction {oc.STREAM_FRAC}); off_mask: executed actions on a zero mask byte",
+                       groups=groups), f, separators=(",", ":"))
+
+
 def main():
     assert po.ref_available(), "build the reference first: make -C oracle ref"
     os.makedirs(OUT, exist_ok=True)
+    if "--offmask" in sys.argv:
+        offmask()
+        return
     if "--bigmaps" in sys.argv:
         bigmaps()
         return

@@ -31,6 +31,10 @@ and max_steps); what a kernel may assume depends on which call came before it.  
             garbage in bytes 5..63, through path "step" | "step_device" | "runner"; the oracle gets
             them clamped to CLAMP, what the engine documents (COG_HAZ_BAD_ACTION)
 
+  ("M", path, steps, seed, kind, frac)   host actions inside their heads that the mask need not allow
+            (tests/offmask_cases.py), through the same three paths; both sides get the same bytes: the
+            reference executes such an action as it stands (environment.cpp:91-181 never reads the mask)
+
 "stored (views)" is po.stored_masks: the record of the agent the agent_selection view shows, which
 a reset leaves alone (vec_environment.h:32-44), as a host loop or sample_policy reads it; the
 stored-mask kernels sample for the env's own agent (0 after a reset), OracleSampler.sample_stored.
@@ -100,6 +104,55 @@ def bad_actions(rng, legal):
     return raw, clamped, hit.any(1)
 
 
+# ---- host actions off the mask (the M op; tests/offmask_cases.py has the cases and their census) ----
+OFFMASK_KINDS = ("single", "replace", "all", "play", "special", "remove", "move", "shop", "sweep")
+_ONE_HEAD = {"play": 0, "special": 1, "remove": 2, "move": 3, "shop": 4}
+SWEEP_SLOTS = tuple((k, v) for k in range(5) for v in range(1, CLAMP[k] + 1))     # 87 (head, value >= 1) pairs
+PRIORITY = (0, 1, 3, 4, 2)            # cog_env::step takes the first non-zero head of play, play_special,
+                                      # move, get_from_shop, remove (environment.cpp:98-171)
+
+
+def executed_head(actions):
+    """The head cog_env::step executes for each (n,) ActionData record, -1 for a pass."""
+    out = np.full(actions.shape[0], -1)
+    for k in reversed(PRIORITY):
+        out = np.where(actions[HEAD_NAMES[k]] != 0, k, out)
+    return out
+
+
+def offmask_actions(rng, legal, kind, frac, t=0, first=0):
+    """From (n,) legal ActionData records: (the records with a random `frac` of the envs altered after
+    `kind`, bool[n]: the env was altered).  Every value stays inside its head (1..CLAMP[k], or 0), so
+    no index is clamped and COG_HAZ_BAD_ACTION stays clear.
+      single   one random head uniform in 1..top, the other heads 0
+      replace  one random head uniform in 1..top, the other heads as sampled
+      all      every head uniform in 0..top
+      play, special, remove, move, shop    `single` with that head
+      sweep    env e takes SWEEP_SLOTS[(first + e + t) % 87] at step t, every env (frac is 1)"""
+    n = legal.shape[0]
+    out = np.zeros(n, dtype=po.ACTION)                       # (bytes 5..63 zero: a copy leaves the padding undefined)
+    top = np.array(CLAMP)
+    u_hit, u_head, u_val = rng.random(n), rng.integers(0, 5, size=n), rng.random((n, 5))
+    if kind == "sweep":
+        hit = np.ones(n, dtype=bool)
+        slot = (first + np.arange(n) + t) % len(SWEEP_SLOTS)
+        head = np.array([s[0] for s in SWEEP_SLOTS])[slot]
+        val = np.array([s[1] for s in SWEEP_SLOTS])[slot][:, None].repeat(5, 1)
+    else:
+        hit = u_hit < frac
+        head = np.full(n, _ONE_HEAD[kind]) if kind in _ONE_HEAD else u_head
+        val = 1 + np.minimum((u_val * top).astype(np.int64), top - 1)          # uniform in 1..top
+    for k, name in enumerate(HEAD_NAMES):
+        if kind == "all":
+            v = np.minimum((u_val[:, k] * (top[k] + 1)).astype(np.int64), top[k])   # uniform in 0..top
+        elif kind == "replace":
+            v = np.where(head == k, val[:, k], legal[name])
+        else:
+            v = np.where(head == k, val[:, k], 0)
+        out[name] = np.where(hit, v, legal[name]).astype(np.uint8)
+    return out, hit
+
+
 def wide_envs(orc):
     """Envs with a card of type >= 8 in some pile of some player (the trio's compact decks cannot
     hold them: such an env parks at step 0 of every trio launch)."""
@@ -126,6 +179,7 @@ class Harness:
         # census (oracle and the host-state mirror alone)
         self.ends, self.op_ends, self.wide_max = 0, [], 0
         self.cdeck, self.trio_loaded, self.trio_clear = False, 0, 0
+        self.m_t, self.census = 0, None                      # M's step clock (sweep); offmask_cases.Census
         if cg is not None:
             kw = self.kw = {} if device is None else {"device": device}
             self.env = cg.vec.get_vec_env(n)(**kw)
@@ -271,6 +325,8 @@ class Harness:
             self.views = True
         elif name == "B":
             self._bad(*args)
+        elif name == "M":
+            self._offmask(*args)
         else:
             self._step_driver(name, *args)
         self.op_ends.append(self.ends - ends0)
@@ -280,6 +336,8 @@ class Harness:
 
     def _step_driver(self, name, steps):
         eng = self.cg is not None
+        if self.census is not None:
+            self.census.entry(self, name)
         m = _CHUNKED.match(name)
         if m or name in ("L", "Ls"):
             kind, chunk = (m.group(1), int(m.group(2))) if m else ("Th" if name == "L" else "Sh", 1)
@@ -371,6 +429,40 @@ class Harness:
             self.last = clamped
             self.orc.step(clamped)
             self._count()
+
+    def _offmask(self, path, steps, seed, kind, frac):
+        eng = self.cg is not None
+        rng = np.random.default_rng(seed)
+        if steps:
+            self.cdeck = False
+        for _ in range(steps):
+            self.osm.sample(self.orc.selected_action_masks)  # the legal records the altered ones replace
+            acts, hit = offmask_actions(rng, self.osm.actions.copy(), kind, frac, self.m_t, self.first)
+            self.m_t += 1
+            if self.census is not None:
+                self.census.before(self, acts, hit)
+            if eng:
+                import torch
+                self.smp.sample(self.env.selected_action_masks)   # (the two samplers stay in step)
+                raw = np.ascontiguousarray(acts).view(np.uint8).reshape(self.n, 64)
+                if path == "step":
+                    self.env.step(acts)
+                elif path == "step_device":
+                    t = torch.from_numpy(raw).to(self.torch_device())
+                    self.env.step_device(t.data_ptr())
+                else:
+                    d = torch.from_dlpack(self.smp.dlpack())
+                    d.copy_(torch.from_numpy(raw))
+                    torch.cuda.synchronize(d.device)         # (the engine's stream reads them next)
+                    r = self.runner(False, False)
+                    r.step()
+                    r.sync()
+                self.acts_fresh = False
+            self.last = acts
+            self.orc.step(acts)
+            self._count()
+            if self.census is not None:
+                self.census.after(self)
 
 
 def run(h: Harness, seq):
@@ -475,5 +567,7 @@ def random_sequence(seed, length=RANDOM_OPS):
 
 
 def for_shards(seq):
-    """The sequence for a handle of several shards: D and G (single-shard by contract) become H."""
+    """The sequence for a handle of several shards: D and G (single-shard by contract) become H, and an
+    M op takes env.step (step_device and the sampler's device actions are one device pointer each)."""
+    seq = [("M", "step") + tuple(op[2:]) if not isinstance(op, str) and op[0] == "M" else op for op in seq]
     return [("H", op[1]) if not isinstance(op, str) and op[0] in SINGLE_SHARD_ONLY else op for op in seq]

@@ -19,6 +19,7 @@ import json
 import sys
 
 import driver_cases as dc
+import offmask_cases as oc
 
 P = dc.PAIR_STEPS                                          # steps per op (30)
 SIZES = (200, 33)
@@ -71,7 +72,7 @@ PLANTED_N = 70
 
 class Row:
     """env: the switches; sizes: the batch sizes it runs at; seq: "rollout" | "rollout+2p" | "redo" |
-    "big" | "host" | "corners" | "corners-host" | "planted" | "planted-host"; kinds: what rollout_kind must say for (players, stored) -> name."""
+    "big" | "host" | "corners" | "corners-host" | "planted" | "planted-host" | "offmask" | "offmask-host"; kinds: what rollout_kind must say for (players, stored) -> name."""
 
     def __init__(self, name, env, seq="rollout", sizes=SIZES, kinds=None):
         self.name, self.env, self.seq, self.sizes = name, dict(env), seq, tuple(sizes)
@@ -124,6 +125,16 @@ ROWS = {r.name: r for r in (
     Row("planted-pipe", {"COG_ROLLOUT": "pipe"}, seq="planted", sizes=(PLANTED_N,), kinds=_all("pipe")),
     Row("planted-wave", {"COG_ROLLOUT": "wave"}, seq="planted", sizes=(PLANTED_N,), kinds=_all("wave")),
     Row("planted-host-no-spec", {"COG_NO_SPEC": "1"}, seq="planted-host", sizes=(PLANTED_N,)),
+    # host actions the mask forbids (tests/offmask_cases.py): a hand-over into the trio and the stored-mask
+    # kernel under the trio's forms, and through the host drivers under the staged publish and masks over PCIe
+    # (these children load torch: the M op writes the sampler's device actions through it)
+    Row("offmask-default", {}, seq="offmask", sizes=(oc.FORM_N,)),
+    Row("offmask-epw32", {"COG_TRIO_EPW": "32"}, seq="offmask", sizes=(oc.FORM_N,)),
+    Row("offmask-wpc1", {"COG_TRIO_WPC": "1"}, seq="offmask", sizes=(oc.FORM_N,)),
+    Row("offmask-wpc2", {"COG_TRIO_WPC": "2"}, seq="offmask", sizes=(oc.FORM_N,)),
+    Row("offmask-no-lat", {"COG_TRIO_JT": "0"}, seq="offmask", sizes=(oc.FORM_N,)),
+    Row("offmask-host-no-zerocopy", {"COG_NO_ZEROCOPY": "1"}, seq="offmask-host", sizes=(oc.FORM_N,)),
+    Row("offmask-host-no-hbm-masks", {"COG_NO_HBM_MASKS": "1"}, seq="offmask-host", sizes=(oc.FORM_N,)),
 )}
 CASES = [(r.name, n) for r in ROWS.values() for n in r.sizes]
 SWITCHES = sorted({k for r in ROWS.values() for k in r.env} | {"COG_SPIN_US", "COG_RUNNER_CHUNK", "COG_DEBUG_PARK_NOFIX"})
@@ -142,6 +153,10 @@ def sequence_of(row):
         return list(CORNERS_SEQ)
     if row.seq == "corners-host":
         return list(CORNERS_HOST_SEQS["one player"])
+    if row.seq == "offmask":
+        return list(oc.FORM_HANDOVER)
+    if row.seq == "offmask-host":
+        return list(oc.FORM_HOST_HANDOVER)
     return list(HOST_SEQ)
 
 
@@ -238,7 +253,8 @@ def child_main(argv):
             out[what.replace(" ", "_") + "_spec_hits"] = int(h.smp.spec_stats()[1])
     else:
         threads = po.host_threads() if n > 4096 else 0
-        h = dc.run(dc.Harness(cg, n, dc.PAIR_SEED, threads=threads), seq)
+        # (the offmask rows: the sampler seed of tests/test_offmask_cpu.py's census of the same walk)
+        h = dc.run(dc.Harness(cg, n, oc.SEED if row.seq.startswith("offmask") else dc.PAIR_SEED, threads=threads), seq)
         h.compare_hazards("at the end")
         if row.seq == "rollout+2p":
             assert h.orc.flags().any(), "the 2-player tail raised no flag on the oracle: the case lost its point"

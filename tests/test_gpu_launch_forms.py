@@ -39,6 +39,11 @@ checks again.
                    COG_TRIO_EPW=32 (lane 5 of the second workgroup), COG_TRIO=0, COG_ROLLOUT=pipe / wave,
                    and under H Hc Hs R1 L Ls with COG_NO_SPEC; the parent searches the cases once and
                    hands them to the child as a file
+  offmask-*        host actions the mask forbids (tests/offmask_cases.py: moves in closed directions, then `all`:
+                   every head uniform in 0..top, on half the envs through env.step, step_device and
+                   runner.step()) handed over to T20 T20 S20 with no switch, COG_TRIO_EPW=32, COG_TRIO_WPC=1
+                   and 2 and COG_TRIO_JT=0, and to H R1 Th20 L Hs Ls under COG_NO_ZEROCOPY and
+                   COG_NO_HBM_MASKS; 200 envs (these children load torch)
   encode           env.time_encode(1, variant) for the production kernel (0), k_encode_lds<false> (1)
                    and k_encode_direct (2): observations equal their copy and the oracle; then the
                    map bytes of the device records are overwritten with 0xEE and the kernel must put
@@ -53,11 +58,12 @@ After a child has ended by a signal, by exit status 134 or 139, at its timeout, 
 HIP memory fault, every remaining case of the module skips with that reason.
 
 Durations on the MI355X (pytest --durations=0, the child's start, import and oracle walk included;
-no child loads torch): a rollout row 0.86-1.21 s at n = 200 and 0.43-0.61 s at 33 (pipe and wave, with
+no child but the offmask-* rows' loads torch): a rollout row 0.86-1.21 s at n = 200 and 0.43-0.61 s at 33 (pipe and wave, with
 their 2-player tail, the longest); redo 0.61-0.72 s; a host row (three harnesses in one child)
 1.70-1.85 s; lat-shared-cu at 16,385 envs 1.73-1.79 s, within the 1.2-3.2 s of the big cases of
 test_gpu_driver_sequences.py; an encode case 0.01-0.25 s (the first one brings torch's GPU side up).
 45 cases, 29 s together.
+The 7 offmask-* rows: 2.1-2.4 s each (torch's import included), 18 s together.
 The 16 corners-* rows: 3.4-3.6 s at n = 200 (8,000 oracle resets at max_steps 0), 0.9-1.3 s at 33, the two host
 rows 2.3-2.5 s; 37 s together.
 
@@ -124,7 +130,9 @@ def run_child(cg, tmp_path, row, n, timeout, extra=()):
     script = tmp_path / "launch_form.py"
     script.write_text(CHILD)
     env = {k: v for k, v in os.environ.items() if k not in lf.SWITCHES and k not in ("COG_ROLLOUT", "COG_TRIO")}
-    env.update(row.env, COG_NO_TORCH="1")                  # (no sequence here has a G or D op)
+    env.update(row.env)
+    if not row.seq.startswith("offmask"):                  # (no other sequence has a G, D or M op)
+        env["COG_NO_TORCH"] = "1"
     what = f"{row.name} at n = {n}"
     try:
         r = subprocess.run([sys.executable, str(script), tests, pkg, oracle_dir, row.name, str(n), *extra], capture_output=True,
