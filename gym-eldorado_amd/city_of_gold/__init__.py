@@ -25,6 +25,9 @@ advantages and returns (GAE over each seat's own rows of each episode), one HIP 
 policy_features(envs, radius) gives the network's input: a flat (n, 208) tensor and an
 (n, 10, W, W) window of the map centred on the seat's own cell, seen from the acting seat (or any
 seat), positions included, float32 or bfloat16, one HIP kernel between the step and the network.
+envs.snapshot() saves the complete state of every env on the GPU (an EnvSnapshot) and
+envs.restore(snap, src) puts it back, or forks it: env j takes snapshot env src[j], for playouts,
+tree search and replay.
 
 All computation runs in libcog_hip.so on a gfx950 GPU.  There is no CPU fallback: creating an
 environment without a usable device raises RuntimeError.
@@ -56,6 +59,7 @@ EASY, MEDIUM, HARD = _C.EASY, _C.MEDIUM, _C.HARD
 from .records import (ActionData, ActionMask, DeckObs, Info, ObsData, PlayerData, PlayerObservation,  # noqa: E402
                       SharedObservation, action_sampler)
 device_count = _C.device_count
+EnvSnapshot = _C.EnvSnapshot           # envs.snapshot() / envs.restore(snap, src): state save, restore and fork
 
 VEC_ENV_CLS = "vec_cog_env_"
 VEC_SAMPLER_CLS = "vec_sampler_"
@@ -98,11 +102,71 @@ def _make_env_cls(n):
             stream = stream_handle(_C.VecEnvBase.shard_info(self, 0)[2])
         _C.VecEnvBase.invalidate_device(self, -1 if stream is None else int(stream))
 
+    def snapshot(self, out=None, stream=None):
+        """The complete state of every env, saved into device memory: an EnvSnapshot (about 4 KB per
+        env, one piece per shard on the shard's device).  out: an EnvSnapshot of the same layout to
+        write into (nothing is allocated); None for a new one.  The copy is enqueued behind the envs'
+        queued work (and, for a single-shard env, behind torch's current stream, or `stream`; -1: no
+        ordering); nothing waits on the host, so it can sit between two runner.rollout launches.
+
+        Saved: everything a step reads -- records, masks, counters, the map, each env's generator, seed,
+        n_players, max_steps and turn counter.  Not saved: the auto-reset switch, samplers, timing."""
+        if out is None:
+            out = EnvSnapshot(self)
+        elif not isinstance(out, EnvSnapshot):
+            raise ValueError("snapshot: out must be an EnvSnapshot")
+        if stream is None and self.num_shards == 1:
+            stream = stream_handle(_C.VecEnvBase.shard_info(self, 0)[2])
+        _C.VecEnvBase.snapshot_raw(self, out, -1 if stream is None else int(stream))
+        return out
+
+    def restore(self, snap, src=None, stream=None):
+        """The envs take the state held in `snap` and go on from it as the saved envs would have, under
+        every driver (step, step_device, runners, rollouts, auto-resets).
+
+        src=None: env i takes snapshot env i; the snapshot's shard layout (counts and devices) must
+        equal the envs'.  src: an (n,) int32, uint32 or int64 torch tensor on the envs' device, env j
+        takes snapshot env src[j]; indices may repeat (a fork), the snapshot may hold more or fewer envs
+        than the handle; envs and snapshot must be single-shard on one device.  The indices are checked
+        on the device before anything is written, and the call waits for that check.  A refused call
+        (ValueError) leaves the envs untouched.
+
+        Ordered after the envs' queued work and torch's current stream (or `stream`; -1: no ordering);
+        like invalidate_device() it returns with the host views (when there are any) refreshed."""
+        if not isinstance(snap, EnvSnapshot):
+            raise ValueError("restore: snap must be an EnvSnapshot")
+        d_src, kind, n_src = 0, 0, 0
+        if src is not None:
+            import torch
+            if self.num_shards != 1 or len(snap.devices) != 1:
+                raise ValueError("restore: src needs a single-shard env and a single-shard snapshot")
+            dev = _C.VecEnvBase.shard_info(self, 0)[2]
+            kinds = {torch.int32: 0, torch.int64: 2}
+            if hasattr(torch, "uint32"):
+                kinds[torch.uint32] = 1
+            if not isinstance(src, torch.Tensor):
+                raise ValueError("restore: src must be a torch tensor")
+            if src.dtype not in kinds:
+                raise ValueError(f"restore: src dtype {src.dtype} is not int32, uint32 or int64")
+            if src.device.type != "cuda" or src.device.index != dev:
+                raise ValueError(f"restore: src is on device {src.device}, the envs are on GPU {dev}")
+            if tuple(src.shape) != (n,) or not src.is_contiguous():
+                raise ValueError(f"restore: src has shape {tuple(src.shape)}, expected a contiguous ({n},)")
+            d_src, kind, n_src = src.data_ptr(), kinds[src.dtype], n
+            if n == 0:
+                d_src = 0
+                if snap.n != 0:
+                    return
+        if stream is None and self.num_shards == 1:
+            stream = stream_handle(_C.VecEnvBase.shard_info(self, 0)[2])
+        _C.VecEnvBase.restore_raw(self, snap, d_src, kind, n_src, -1 if stream is None else int(stream))
+
     doc = (f"Vectorized city of gold environment for {n} environments.\n\n"
            "reset() must be called first to initialize the environments before stepping.")
     return type(VEC_ENV_CLS + str(n), (_C.VecEnvBase,), {"__init__": __init__, "__doc__": doc,
                                                          "step_device": step_device,
                                                          "invalidate_device": invalidate_device,
+                                                         "snapshot": snapshot, "restore": restore,
                                                          "__module__": "city_of_gold.vec.sampler"})
 
 
@@ -530,4 +594,4 @@ del _n, _m
 __all__ = ["vec", "Difficulty", "EASY", "MEDIUM", "HARD", "ObsData", "ActionMask", "ActionData", "Info",
            "DeckObs", "SharedObservation", "PlayerData", "PlayerObservation", "action_sampler", "get_vec_env",
            "get_vec_sampler", "get_runner", "device_count", "device_tensors", "stream_handle", "cog_env", "policy_evaluate",
-           "mask_records", "turn_gae", "policy_features"]
+           "mask_records", "turn_gae", "policy_features", "EnvSnapshot"]

@@ -371,6 +371,23 @@ struct cog_runner {
   int chunk = 1;                      // rollout steps per launch (>1: persistent K-step kernel)
 };
 
+// A state snapshot (cog.h): per shard one block of cog::kSnapBytes records on the shard's device,
+// and the event of the last save into it, which a restore on another handle's stream waits for.
+// Restores end with the host waiting for them, so a save never has to wait for a reader.
+struct SnapShard {
+  int device = 0;
+  size_t n = 0;
+  uint8_t *rec = nullptr;
+  hipEvent_t ev = nullptr;
+  bool saved = false;
+};
+struct cog_snapshot {
+  size_t n = 0;
+  uint8_t n_players = 4;              // cog_env::n_players / max_steps at the last save
+  uint32_t max_steps = 0;
+  std::vector<SnapShard> sh;
+};
+
 namespace {
 
 bool single(const cog_env *e) { return e->sh.size() == 1; }
@@ -1867,6 +1884,164 @@ int cog_runner_kernel_time(cog_runner *r, double *total_ms, uint64_t *launches) 
   r->ev_used = 0;
   r->timed_launches = 0;
   return COG_OK;
+}
+
+// ---- state snapshots ---------------------------------------------------------------------
+static void snapshot_free(cog_snapshot *p) {
+  if (!p) return;
+  for (SnapShard &q : p->sh) {
+    DeviceGuard g(q.device);
+    if (q.ev) {
+      (void)hipEventSynchronize(q.ev);                     // (a save still running on a live handle's stream)
+      (void)hipEventDestroy(q.ev);
+    }
+    if (q.rec) (void)hipFree(q.rec);
+  }
+  delete p;
+}
+
+static bool same_layout(const cog_env *e, const cog_snapshot *p) {
+  if (e->n != p->n || e->sh.size() != p->sh.size()) return false;
+  for (size_t j = 0; j < e->sh.size(); j++)
+    if (e->sh[j].n != p->sh[j].n || e->sh[j].device != p->sh[j].device) return false;
+  return true;
+}
+
+int cog_env_snapshot_create(cog_env *env, cog_snapshot **out) {
+  if (!env || !out) return fail(COG_ERR_INVALID, "NULL argument");
+  *out = nullptr;
+  cog_snapshot *p = new cog_snapshot();
+  p->n = env->n;
+  p->n_players = env->n_players;
+  p->max_steps = env->max_steps;
+  p->sh.resize(env->sh.size());
+  for (size_t j = 0; j < env->sh.size(); j++) {
+    SnapShard &q = p->sh[j];
+    q.device = env->sh[j].device;
+    q.n = env->sh[j].n;
+    DeviceGuard g(q.device);
+    int rc = dmalloc(&q.rec, q.n * cog::kSnapBytes);
+    if (!rc && hipEventCreateWithFlags(&q.ev, hipEventDisableTiming) != hipSuccess) rc = fail(COG_ERR_HIP, "hipEventCreate failed");
+    if (rc) {
+      snapshot_free(p);
+      return rc;
+    }
+  }
+  *out = p;
+  return COG_OK;
+}
+
+void cog_snapshot_destroy(cog_snapshot *snap) { snapshot_free(snap); }
+
+int cog_snapshot_info(const cog_snapshot *snap, size_t *n, int *n_shards, size_t *bytes, int *n_players,
+                      uint32_t *max_steps) {
+  if (!snap) return fail(COG_ERR_INVALID, "snapshot is NULL");
+  if (n) *n = snap->n;
+  if (n_shards) *n_shards = (int)snap->sh.size();
+  if (bytes) *bytes = snap->n * cog::kSnapBytes;
+  if (n_players) *n_players = snap->n_players;
+  if (max_steps) *max_steps = snap->max_steps;
+  return COG_OK;
+}
+
+int cog_snapshot_shard_info(const cog_snapshot *snap, int k, size_t *count, int *device) {
+  if (!snap || k < 0 || (size_t)k >= snap->sh.size()) return fail(COG_ERR_INVALID, "snapshot shard index out of range");
+  if (count) *count = snap->sh[k].n;
+  if (device) *device = snap->sh[k].device;
+  return COG_OK;
+}
+
+// A save reads the handle's arrays and writes the snapshot alone: one kernel per shard behind the
+// shard's queued work, no wait, no change of the handle's host-side state.
+int cog_env_snapshot(cog_env *env, cog_snapshot *snap, void *stream) {
+  if (!env || !snap) return fail(COG_ERR_INVALID, "NULL argument");
+  if (!same_layout(env, snap))
+    return fail(COG_ERR_INVALID, "snapshot: the snapshot's shard layout (counts and devices) differs from the env's");
+  for (size_t j = 0; j < env->sh.size(); j++) {
+    EnvShard &k = env->sh[j];
+    SnapShard &q = snap->sh[j];
+    DeviceGuard g(k.device);
+    if (stream != COG_NO_STREAM) {
+      HIPCHK(hipEventRecord(k.ev, static_cast<hipStream_t>(stream)));
+      HIPCHK(hipStreamWaitEvent(k.stream, k.ev, 0));
+    }
+    if (cog::launch_state_save(k.s, q.rec, k.stream))
+      return fail(COG_ERR_HIP, std::string("snapshot launch failed: ") + hipGetErrorString(hipGetLastError()));
+    HIPCHK(hipEventRecord(q.ev, k.stream));
+    q.saved = true;
+  }
+  snap->n_players = env->n_players;
+  snap->max_steps = env->max_steps;
+  return COG_OK;
+}
+
+// A restore is a stronger cog_env_invalidate_device: every array a step reads is replaced, so the
+// state is arbitrary for everything the host remembers of the shard (no lean clock, no compact
+// decks, no speculative sample, stale host views with every map to publish again).
+int cog_env_restore(cog_env *env, const cog_snapshot *snap, const void *d_src, int src_kind, size_t n_src, void *stream) {
+  if (!env || !snap) return fail(COG_ERR_INVALID, "NULL argument");
+  for (const SnapShard &q : snap->sh)
+    if (q.n && !q.saved) return fail(COG_ERR_INVALID, "restore: nothing was saved into this snapshot yet");
+  if (d_src) {
+    if (!single(env) || snap->sh.size() != 1)
+      return fail(COG_ERR_INVALID, "restore: src needs a single-shard env and a single-shard snapshot");
+    if (env->sh[0].device != snap->sh[0].device)
+      return fail(COG_ERR_INVALID, "restore: the env and the snapshot are on different devices");
+    if (src_kind != COG_SRC_I32 && src_kind != COG_SRC_U32 && src_kind != COG_SRC_I64)
+      return fail(COG_ERR_INVALID, "restore: unknown src kind " + std::to_string(src_kind));
+    if (n_src != env->n) return fail(COG_ERR_INVALID, "restore: src length != num_envs");
+    if (reinterpret_cast<uintptr_t>(d_src) % (src_kind == COG_SRC_I64 ? 8 : 4))
+      return fail(COG_ERR_INVALID, "restore: src pointer is not aligned to its element size");
+    hipPointerAttribute_t at{};
+    if (env->n && (hipPointerGetAttributes(&at, d_src) != hipSuccess || at.type != hipMemoryTypeDevice ||
+                   at.device != env->sh[0].device)) {
+      (void)hipGetLastError();
+      return fail(COG_ERR_INVALID, "restore: src is not device memory of the env's device");
+    }
+  } else if (!same_layout(env, snap)) {
+    return fail(COG_ERR_INVALID, "restore: the snapshot's shard layout (counts and devices) differs from the env's");
+  }
+  int rc;
+  if (d_src && env->n) {                                   // every index, before anything is written
+    EnvShard &k = env->sh[0];
+    DeviceGuard g(k.device);
+    if (stream != COG_NO_STREAM) {                         // the caller's stream produced src
+      HIPCHK(hipEventRecord(k.ev, static_cast<hipStream_t>(stream)));
+      HIPCHK(hipStreamWaitEvent(k.stream, k.ev, 0));
+    }
+    volatile uint32_t *bad = env->h_err + 16;              // word 16 of shard 0's pinned line (0: error, 32: completion)
+    *bad = 0u;
+    if (cog::launch_src_check(d_src, src_kind, env->n, snap->n, k.s.err + 16, k.stream))
+      return fail(COG_ERR_HIP, std::string("restore launch failed: ") + hipGetErrorString(hipGetLastError()));
+    HIPCHK(hipStreamSynchronize(k.stream));
+    if (*bad) {
+      *bad = 0u;
+      return fail(COG_ERR_INVALID, "restore: a src index is outside the snapshot's " + std::to_string(snap->n) + " envs");
+    }
+  }
+  if ((rc = prepare_host(env))) return rc;
+  env_changed(env);                                        // (voids a speculative sample)
+  env->n_players = snap->n_players;
+  env->max_steps = snap->max_steps;
+  for (size_t j = 0; j < env->sh.size(); j++) {
+    EnvShard &k = env->sh[j];
+    const SnapShard &q = snap->sh[d_src ? 0 : j];
+    DeviceGuard g(k.device);
+    views_pending(k);
+    k.mir_valid = false;                                   // (the next publish stores every granule)
+    k.lean_clock = ~0ull;                                  // (any state: the trio carries its fix-up)
+    k.cdeck_ok = false;
+    if (!k.n) continue;
+    HIPCHK(hipStreamWaitEvent(k.stream, q.ev, 0));         // the save, whichever stream ran it
+    if (cog::launch_state_restore(k.s, q.rec, d_src, src_kind, k.stream))
+      return fail(COG_ERR_HIP, std::string("restore launch failed: ") + hipGetErrorString(hipGetLastError()));
+    // the host views' maps follow the dirty list, which a restore does not feed: every map
+    if (env->host)
+      HIPCHK(hipMemcpy2DAsync(env->h_obs + k.first, COG_OBS_BYTES, k.s.obs, COG_OBS_BYTES, COG_OBS_MAP_BYTES, k.n,
+                              hipMemcpyDeviceToHost, k.stream));
+  }
+  if ((rc = finish(env, true))) return rc;
+  return env->host ? sync_all(env) : COG_OK;               // (the map copies)
 }
 
 }  // extern "C"

@@ -223,6 +223,29 @@ int launch_seed_sampler(size_t n, uint64_t seed, size_t first, uint32_t *d_rng, 
 // completion word: stores seq into *d_word (device address of a pinned host word) once every
 // earlier packet of the stream has completed
 int launch_signal(uint32_t *d_word, uint32_t seq, void *stream);
+
+// State snapshots (engine/state_copy.h).  One record of kSnapBytes per env, whole 64-B blocks: the
+// dynamic tail of the ObsData record, the selected mask, Info, rewards, EnvPriv, the five mask bit
+// vectors, done and agent (one granule), padding up to the next 64-B block, then the compact code
+// grid.  The 16,128-B map observation is not saved (the restore encodes it from the code grid),
+// nor are `grid` and `gen`, which only map generation reads: it clears the box EnvPriv names
+// first, so the restore zeroes the destination's old box and leaves `grid` empty.
+constexpr size_t kSnapTail = 0, kSnapSel = kSnapTail + (COG_OBS_BYTES - COG_OBS_MAP_BYTES);
+constexpr size_t kSnapInfo = kSnapSel + COG_MASK_BYTES, kSnapRew = kSnapInfo + COG_INFO_BYTES;
+constexpr size_t kSnapPriv = kSnapRew + 16, kSnapHeads = kSnapPriv + sizeof(EnvPriv);
+constexpr size_t kSnapMisc = kSnapHeads + 5 * 16;        // byte 0 done, byte 1 agent
+constexpr size_t kSnapCgrid = (kSnapMisc + 16 + 63) & ~(size_t)63;
+constexpr size_t kSnapBytes = kSnapCgrid + COG_CELLS;
+static_assert(kSnapSel % 16 == 0 && kSnapCgrid == 1728 && kSnapBytes == 4032 && kSnapBytes % 64 == 0, "snapshot record");
+enum SrcKind : int { SRC_I32 = 0, SRC_U32 = 1, SRC_I64 = 2 };
+// every env's record from the handle's arrays: a coalesced copy (`snap`: s.n records)
+int launch_state_save(const DevState &s, uint8_t *snap, void *stream);
+// *bad (device address of a zeroed word) becomes 1 when an entry of src[0 .. n) is outside [0, n_snap)
+int launch_src_check(const void *src, int src_kind, size_t n, size_t n_snap, uint32_t *bad, void *stream);
+// env j of the handle takes record src[j] (src null: record j): the arrays a step reads are
+// written from it, the map observation is encoded from its code grid, and the box of the env's
+// old map is cleared from `grid`.  No index is checked here (launch_src_check).
+int launch_state_restore(const DevState &s, const uint8_t *snap, const void *src, int src_kind, void *stream);
 // variant bit 0: non-temporal loads/stores; bit 4: one granule per work-item (bits 1-3 ignored);
 // bit 1: 32 waves per CU instead of 8 (grid stride);
 // bit 2: one pass, 32 KiB per workgroup (bit 1 ignored); bit 3: the encode's 1:7 read:write mix

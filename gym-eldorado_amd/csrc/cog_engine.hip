@@ -28,6 +28,8 @@
 //   k_publish        changed granules of the host-visible records to the pinned views
 //   k_sync_heads, k_resync   mask bit-vectors of every env from its byte records (init / reset)
 //   k_signal, k_seed_sampler, k_copy_peak / _block / _one, k_stream_mix   completion word, sampler seeds, copy probes
+//   k_state_save, k_src_check, k_state_restore   state snapshots: save, index check, restore / fork with the
+//                    map observation encoded again (engine/state_copy.h, included last)
 //
 // One translation unit on purpose (the step inlines into every driver; one two-minute compile): the
 // parts are not separately compilable.  The order of the text, and of the launchers' first mention of
@@ -3219,5 +3221,8 @@ int launch_seed_sampler(size_t n, uint64_t seed, size_t first, uint32_t *d_rng, 
                      d_rng);
   return launched();
 }
+
+// last, so that the kernels above keep their places in the code object ("Source layout")
+#include "engine/state_copy.h"     // state snapshots: k_state_save, k_state_restore and their launchers
 
 }  // namespace cog

@@ -250,6 +250,37 @@ class VecEnv {
   cog_env *h_ = nullptr;
 };
 
+// ---- state snapshot (cog.h cog_snapshot): owns its device memory, not tied to the env's life ---
+class Snapshot {
+ public:
+  explicit Snapshot(VecEnv &env) { check(cog_env_snapshot_create(env.handle(), &h_)); }
+  ~Snapshot() { cog_snapshot_destroy(h_); }
+  Snapshot(const Snapshot &) = delete;
+  Snapshot &operator=(const Snapshot &) = delete;
+  cog_snapshot *handle() const { return h_; }
+  size_t n() const { size_t v = 0; check(cog_snapshot_info(h_, &v, nullptr, nullptr, nullptr, nullptr)); return v; }
+  size_t nbytes() const { size_t v = 0; check(cog_snapshot_info(h_, nullptr, nullptr, &v, nullptr, nullptr)); return v; }
+  int n_players() const { int v = 0; check(cog_snapshot_info(h_, nullptr, nullptr, nullptr, &v, nullptr)); return v; }
+  uint32_t max_steps() const { uint32_t v = 0; check(cog_snapshot_info(h_, nullptr, nullptr, nullptr, nullptr, &v)); return v; }
+  std::vector<int> devices() const {
+    int k = 0;
+    check(cog_snapshot_info(h_, nullptr, &k, nullptr, nullptr, nullptr));
+    std::vector<int> out(k);
+    for (int j = 0; j < k; j++) check(cog_snapshot_shard_info(h_, j, nullptr, &out[j]));
+    return out;
+  }
+  std::vector<size_t> counts() const {
+    int k = 0;
+    check(cog_snapshot_info(h_, nullptr, &k, nullptr, nullptr, nullptr));
+    std::vector<size_t> out(k);
+    for (int j = 0; j < k; j++) check(cog_snapshot_shard_info(h_, j, &out[j], nullptr));
+    return out;
+  }
+
+ private:
+  cog_snapshot *h_ = nullptr;
+};
+
 // ---- vec sampler (py_vec_action_sampler, vectorized.h:107-127) ----------------------------
 class VecSampler {
  public:
@@ -533,6 +564,16 @@ PYBIND11_MODULE(_city_of_gold, m) {
         // after the work queued on `stream` (-1: no ordering)
         check(cog_env_invalidate_device(e.handle(), stream < 0 ? COG_NO_STREAM : reinterpret_cast<void *>((uintptr_t)stream)));
       }, "stream"_a = -1)
+      .def("snapshot_raw", [](VecEnv &e, Snapshot &snap, int64_t stream) {
+        // cog_env_snapshot into `snap`, ordered after the work queued on `stream` (-1: no ordering)
+        check(cog_env_snapshot(e.handle(), snap.handle(), stream < 0 ? COG_NO_STREAM : reinterpret_cast<void *>((uintptr_t)stream)));
+      }, "snap"_a, "stream"_a = -1)
+      .def("restore_raw", [](VecEnv &e, const Snapshot &snap, uintptr_t d_src, int src_kind, size_t n_src, int64_t stream) {
+        // cog_env_restore: d_src 0 for the whole batch, else n_src indices of src_kind (0 int32,
+        // 1 uint32, 2 int64) in device memory, ordered after `stream` (-1: no ordering)
+        check(cog_env_restore(e.handle(), snap.handle(), reinterpret_cast<const void *>(d_src), src_kind, n_src,
+                              stream < 0 ? COG_NO_STREAM : reinterpret_cast<void *>((uintptr_t)stream)));
+      }, "snap"_a, "d_src"_a = 0, "src_kind"_a = 0, "n_src"_a = 0, "stream"_a = -1)
       .def("policy_features_raw", [](VecEnv &e, int radius, int dtype, int seat_mode, int seat, uintptr_t d_seats,
                                      uintptr_t d_vec, uintptr_t d_local, int64_t stream) {
         // cog_env_policy_features over raw device pointers (city_of_gold policy_features is the torch
@@ -565,6 +606,16 @@ PYBIND11_MODULE(_city_of_gold, m) {
         check(cog_env_time_encode(e.handle(), iters, variant, &ms));
         return ms;
       }, "iters"_a = 20, "variant"_a = 0);
+
+  py::class_<Snapshot>(m, "EnvSnapshot",
+                       "The complete state of every env of a vec env at one point, in device memory (envs.snapshot()).")
+      .def(py::init<VecEnv &>(), "env"_a, "an empty snapshot with the env's layout (envs.snapshot() fills one)")
+      .def_property_readonly("n", &Snapshot::n, "envs held")
+      .def_property_readonly("nbytes", &Snapshot::nbytes, "device memory over all shards")
+      .def_property_readonly("n_players", &Snapshot::n_players)
+      .def_property_readonly("max_steps", &Snapshot::max_steps)
+      .def_property_readonly("devices", &Snapshot::devices, "the device of every shard's piece")
+      .def_property_readonly("counts", &Snapshot::counts, "the envs of every shard's piece");
 
   py::class_<VecSampler>(m, "VecSamplerBase", py::dynamic_attr())
       .def(py::init<size_t, std::optional<size_t>, const py::object &, uint64_t>(), "n_envs"_a, "seed"_a = py::none(),

@@ -190,6 +190,45 @@ COG_API int cog_env_signal_stream(cog_env *env, int shard, void *stream);
  * this call, writes to those records are not seen by the next step (see INTEGRATION.md "Device
  * views"). */
 COG_API int cog_env_invalidate_device(cog_env *env, void *stream);
+
+/* ---- state snapshots: save, restore and fork on the GPU ----------------------------------- */
+/* An opaque copy of the complete state of every env of a handle, in device memory, one piece per
+ * shard on the shard's device (about 4 KB per env: everything but the map observation, which a
+ * restore encodes again).  The env's generator, seed, parameters and turn counter travel with it:
+ * a restored env goes on exactly as the saved one would, under every driver.  Not in it: the
+ * handle's auto-reset switch, samplers, timing.  A snapshot is independent of the handle it came
+ * from (that handle may be destroyed) and may be restored any number of times, into any handle of
+ * the same layout.
+ *
+ * cog_env_snapshot_create allocates a snapshot with env's layout (shard counts and devices).
+ * cog_env_snapshot is enqueued on the shards' streams after their queued work (and after the work
+ * queued on `stream`, COG_NO_STREAM: none) and returns without waiting; the handle's layout must
+ * equal the snapshot's.  A snapshot of a handle that was never reset holds the default state.
+ *
+ * cog_env_restore: with d_src NULL env i takes snapshot env i (equal layouts).  With d_src, n_src
+ * == num_envs indices in the env's device memory, of type src_kind, ordered after `stream`: env j
+ * takes snapshot env d_src[j]; indices may repeat (a fork) and the snapshot may hold more or fewer
+ * envs than the handle; both must be single-shard, on one device.  Every index is checked on the
+ * device before anything is written, and the call waits for that check: an index outside the
+ * snapshot, like every other refusal, returns COG_ERR_INVALID with the handle untouched.  A restore
+ * ends as cog_env_invalidate_device does: host views (maps included) refreshed when the env has
+ * them, the call complete on return.  The handle's batch parameters (players, max_steps) become
+ * the snapshot's.  The sticky device status words are left alone (errors are reported by the call
+ * that meets them); cog_env_hazards reads the per-env flags, which are restored. */
+typedef struct cog_snapshot cog_snapshot;
+#define COG_SRC_I32 0
+#define COG_SRC_U32 1
+#define COG_SRC_I64 2
+COG_API int cog_env_snapshot_create(cog_env *env, cog_snapshot **out);
+COG_API int cog_env_snapshot(cog_env *env, cog_snapshot *snap, void *stream);
+COG_API int cog_env_restore(cog_env *env, const cog_snapshot *snap, const void *d_src, int src_kind, size_t n_src,
+                            void *stream);
+/* any out pointer may be NULL; bytes: device memory over all shards; n_players, max_steps: the
+ * batch parameters of the handle at the last cog_env_snapshot (of its creation before) */
+COG_API int cog_snapshot_info(const cog_snapshot *snap, size_t *n, int *n_shards, size_t *bytes, int *n_players,
+                              uint32_t *max_steps);
+COG_API int cog_snapshot_shard_info(const cog_snapshot *snap, int shard, size_t *count, int *device);
+COG_API void cog_snapshot_destroy(cog_snapshot *snap);
 /* diagnostics: re-run the map-observation encode (map.cpp:389-405) over all envs `iters`
  * times back to back; average device time per launch (HIP events).  Output is unchanged.
  * variant: 0 = production kernel, >0 = alternative implementations kept for A/B timing. */
